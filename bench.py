@@ -2,7 +2,26 @@
 """Throughput benchmark of the affine-ME hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
-                    [--qp QP] [--frames F] [--no-cpu-baseline] [--no-spans]
+                    [--qp QP] [--frames F] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-spans] [--fs-frames F]]
+
+A plain run does what the headline figure needs and no more: it sets up, warms
+up, times the K steps (no events inside them), writes the last step's results
+with --dump-outputs, and prints the contract line (metric, value, unit,
+ms_per_step, the workload).  Everything else this file measures or checks --
+the per-kernel events and `roofline`, the per-step spread `step_ms`, the
+`gather` of the decision records with rank 0's recompute check, `frame_shard`,
+and the CPU baseline with its bit-exact `parity_sample` -- runs only with
+--full, which adds those records to the line.
+
+--dump-outputs DIR writes what the last timed step computed, the arrays a
+caller of vame_affine_me_batch receives, in job / refIdx / mode order:
+DIR/cost.npy (float64 [rows], gBestCost) and DIR/cpmv.npy (float32 [rows, 7],
+nCPs + the six CPMV components; exact, the values are far below 2^24); with N
+ranks every rank writes DIR/rank<k>_cost.npy / _cpmv.npy.  Above 60 MB in all
+(c3-c5) a fixed, seeded sample of the rows is written, and DIR/rows.npy holds
+their indices.  The inputs are synthesized from a fixed seed, so two builds
+run with the same arguments can be compared output for output.
 
 One step = the hot path over one batch of synthetic input: every (POC, refIdx)
 pair of this rank's POCs (refs from the reference's 4-slot ring, lambda from
@@ -27,10 +46,10 @@ frames of its own share, with no collective on the data path.
                converge more slowly: a content effect, not a scaling one);
   c5           scales strongly: 240 POCs of 3840x2160 in all (configs[4]),
                contiguous pair blocks of one sequence.
-After the timed steps the decision records go to rank 0 in one RCCL gather
-(pack and exchange timed apart and reported as `gather`), and rank 0
-recomputes the first and last POC of every rank's block and checks the
-gathered records byte for byte.  Every line (N = 1 too) then carries
+With --full, after the timed steps the decision records go to rank 0 in one
+RCCL gather (pack and exchange timed apart and reported as `gather`), and rank
+0 recomputes the first and last POC of every rank's block and checks the
+gathered records byte for byte.  Every --full line (N = 1 too) then carries
 `frame_shard`: north star's frame shard of ONE 3840x2160 sequence
 (--fs-frames, default 48 POCs = 186 pairs) over the N ranks with the gather
 into rank 0 inside its timed span.  Rank 0 prints one JSON line.
@@ -93,6 +112,12 @@ def main():
                     help="sequence length (c5: total POCs; c2-c4: POCs per GPU)")
     ap.add_argument("--weak", default="streams", choices=("streams", "sequence"),
                     help="weak-scaling data (c2-c4): a sequence per rank, or pair blocks of one sequence")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel "
+                         "events and roofline, step spread, gather + recompute check, frame_shard, "
+                         "CPU baseline + parity sample")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--rank-only", type=int, default=None, metavar="K",
                     help="diagnostic: run only rank K's block of a --gpus N job, alone on GPU 0 "
@@ -184,7 +209,9 @@ def main():
     # kernels are timed on extra steps after them (timing their dispatches too
     # cost ~0.7 % of a c2 step).  Diagnostic override VAME_BENCH_KTIMING: 0 = no
     # events, 1 = every kernel in the timed steps.
-    ktiming = int(os.environ.get("VAME_BENCH_KTIMING", "2"))
+    # A plain run (no --full) records no events at all: its timed span holds
+    # the steps alone.
+    ktiming = int(os.environ.get("VAME_BENCH_KTIMING", "2")) if args.full else 0
     # the events ride on a sample of the timed steps -- every ksample-th step
     # (VAME_BENCH_KSAMPLE, default 4) -- so the timed span carries a quarter of
     # their cost (in the engine's one-stream mode a dispatch with events costs
@@ -198,7 +225,10 @@ def main():
     every_step = os.environ.get("VAME_BENCH_STEPEV", "sampled") == "all"
     step_ev = []
     t_start = time.perf_counter()
-    for i in range(args.steps):
+    if not args.full:  # the steps alone
+        for _ in range(args.steps):
+            run.step()
+    for i in range(args.steps if args.full else 0):  # --full: the steps with their sampled events
         sampled = i % ksample == 0
         bracket = every_step or (i % ksample == (1 if ksample > 1 else 0))
         if ksample > 1:
@@ -212,6 +242,86 @@ def main():
             step_ev.append((a_, b_))
     barrier()
     elapsed = time.perf_counter() - t_start
+
+    def all_reduce(vals, op):
+        if dist is None:
+            return vals
+        on = dev if dist.get_backend() == "nccl" else torch.device("cpu")
+        t = torch.tensor(vals, dtype=torch.float64, device=on)
+        dist.all_reduce(t, op=op)
+        return t.tolist()
+
+    ops = getattr(dist, "ReduceOp", None)
+    tmax = all_reduce([elapsed], ops and ops.MAX)[0]
+    # whole-job totals: rows, in-frame rows, compulsory bytes (orig + ref frame + results per pair)
+    rows_total, inframe_total, compulsory_total = all_reduce(
+        [float(rows_per_step * args.steps), float(run.pairs * acc["rows_inframe"] * args.steps),
+         float(run.pairs * (2 * W * H * 2 + acc["rows"] * 36) * args.steps)], ops and ops.SUM)
+    value = rows_total / tmax
+
+    # the contract line of every run; --full adds its records below
+    result = {
+        "metric": "candidate CU-blocks/s at 1080p QP32; bit-exact CPMV/cost match vs reference",
+        "value": value,
+        "unit": "CU-blocks/s",
+        "n_gpus": 1 if args.rank_only is not None else world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "prewarm": {"seconds": args.prewarm_s, "steps": prewarm_steps},
+        "ms_per_step": tmax * 1e3 / args.steps,
+        "full": args.full,
+        "world": {"size": world, "backend": "none" if dist is None else dist.get_backend(),
+                  "launcher": os.environ.get("VAME_LAUNCHER", "external" if world > 1 else "none"),
+                  # VAME_FORCE_PG=1: a one-rank process group, so the N-GPU
+                  # collectives (init, all_reduce, gather) run on one GPU
+                  "forced_pg": args.rank_only is None and world == 1 and dist is not None},
+        "higher_is_better": True,
+        "scaling": cfg["scaling"],
+        # which multi-GPU form this line measures (DESIGN §6): weak scaling over
+        # independent sequences ("streams", the default) or over pair blocks
+        # of one sequence ("sequence"); c5 is the north star's frame shard of
+        # one 240-frame sequence (strong scaling); every --full line also
+        # carries the frame shard of one 2160p sequence (`frame_shard`)
+        "scaling_form": ("streams" if streams else "sequence") if weak else "frame-shard",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic",
+        "config": {"workload": cfg["label"], "resolution": f"{W}x{H}", "qp": qp,
+                   "sequence_frames": n_frames, "sequence_pairs": n_pairs or sequence_pairs(n_frames),
+                   "pocs_rank0": len(run.pocs),
+                   "pairs_per_step_rank0": run.pairs, "rows_per_step_rank0": rows_per_step,
+                   "rows_per_step_all": rows_total / args.steps,
+                   "modes": "2cp+3cp" if modes & 2 else "2cp",
+                   "parallelism": (f"frame-shard x{world} (a sequence of its own per rank)" if streams else
+                                   f"frame-shard x{world} (pair_shard of one sequence)"),
+                   "scaling_form_note": ("N independent sequences (each rank codes the 1-GPU config "
+                                         "on its own synthetic sequence); the frame shard of one "
+                                         "sequence is `frame_shard` (and --config c5)" if streams else
+                                         "the first P x N pairs of one sequence in contiguous pair "
+                                         "blocks (deeper POCs on higher ranks)" if weak else
+                                         "240 POCs of one sequence in contiguous pair blocks over "
+                                         "the ranks"),
+                   **({"rank_only": {"rank": rank, "of": world}} if args.rank_only is not None else {})},
+        # SURVEY §8(d) companions: in-frame candidates (the rows the kernels
+        # predict; out-of-frame rows are logged with their initial cost) and the
+        # compulsory bytes (orig + ref frame + results per pair) over the step
+        "value_inframe": inframe_total / tmax,
+        "compulsory": {"bytes_per_step_all": compulsory_total / args.steps,
+                       "GBps": compulsory_total / tmax / 1e9 if tmax > 0 else 0.0},
+    }
+    result["native"] = native_record()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run, f"rank{rank}_" if world > 1 else "")
+    if not args.full:
+        eng.close()
+        if dist is not None:
+            dist.barrier()
+        if rank == 0 or args.rank_only is not None:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     step_ms = sorted(a_.elapsed_time(b_) for a_, b_ in step_ev)
     if not step_ms:  # fewer timed steps than one sample period
         step_ms = [elapsed * 1e3 / max(args.steps, 1)]
@@ -235,22 +345,6 @@ def main():
         big_on = f"{big_steps} untimed steps after the timed ones"
     eng.set_timing(False)
     span_ms, span_n = (0.0, 0) if args.no_spans else span_step()
-
-    def all_reduce(vals, op):
-        if dist is None:
-            return vals
-        on = dev if dist.get_backend() == "nccl" else torch.device("cpu")
-        t = torch.tensor(vals, dtype=torch.float64, device=on)
-        dist.all_reduce(t, op=op)
-        return t.tolist()
-
-    ops = getattr(dist, "ReduceOp", None)
-    tmax = all_reduce([elapsed], ops and ops.MAX)[0]
-    # whole-job totals: rows, in-frame rows, compulsory bytes (orig + ref frame + results per pair)
-    rows_total, inframe_total, compulsory_total = all_reduce(
-        [float(rows_per_step * args.steps), float(run.pairs * acc["rows_inframe"] * args.steps),
-         float(run.pairs * (2 * W * H * 2 + acc["rows"] * 36) * args.steps)], ops and ops.SUM)
-    value = rows_total / tmax
 
     # the one exchange step, outside the timed steps: decision records to rank 0
     # (a --rank-only diagnostic has no other ranks: it checks its own block).
@@ -398,61 +492,14 @@ def main():
                              "alg_bytes_per_launch": step_bytes / max(span_n, 1)},
     }
 
-    result = {
-        "metric": "candidate CU-blocks/s at 1080p QP32; bit-exact CPMV/cost match vs reference",
-        "value": value,
-        "unit": "CU-blocks/s",
-        "n_gpus": 1 if args.rank_only is not None else world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "prewarm": {"seconds": args.prewarm_s, "steps": prewarm_steps},
-        "ms_per_step": tmax * 1e3 / args.steps,
+    result.update({
         # rank 0's per-step GPU times (HIP events around the timed steps that
         # carry no kernel-timing events)
         "step_ms": {"median": step_ms[len(step_ms) // 2], "min": step_ms[0], "max": step_ms[-1],
                     "steps": len(step_ms)},
-        "world": {"size": world, "backend": "none" if dist is None else dist.get_backend(),
-                  "launcher": os.environ.get("VAME_LAUNCHER", "external" if world > 1 else "none"),
-                  # VAME_FORCE_PG=1: a one-rank process group, so the N-GPU
-                  # collectives (init, all_reduce, gather) run on one GPU
-                  "forced_pg": args.rank_only is None and world == 1 and dist is not None},
-        "higher_is_better": True,
-        "scaling": cfg["scaling"],
-        # which multi-GPU form this line measures (DESIGN §6): weak scaling over
-        # independent sequences ("streams", the default) or over pair blocks
-        # of one sequence ("sequence"); c5 is the north star's frame shard of
-        # one 240-frame sequence (strong scaling); every line also carries the
-        # frame shard of one 2160p sequence (`frame_shard`)
-        "scaling_form": ("streams" if streams else "sequence") if weak else "frame-shard",
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": "synthetic",
-        "config": {"workload": cfg["label"], "resolution": f"{W}x{H}", "qp": qp,
-                   "sequence_frames": n_frames, "sequence_pairs": n_pairs or sequence_pairs(n_frames),
-                   "pocs_rank0": len(run.pocs),
-                   "pairs_per_step_rank0": run.pairs, "rows_per_step_rank0": rows_per_step,
-                   "rows_per_step_all": rows_total / args.steps,
-                   "modes": "2cp+3cp" if modes & 2 else "2cp",
-                   "parallelism": (f"frame-shard x{world} (a sequence of its own per rank)" if streams else
-                                   f"frame-shard x{world} (pair_shard of one sequence)"),
-                   "scaling_form_note": ("N independent sequences (each rank codes the 1-GPU config "
-                                         "on its own synthetic sequence); the frame shard of one "
-                                         "sequence is `frame_shard` (and --config c5)" if streams else
-                                         "the first P x N pairs of one sequence in contiguous pair "
-                                         "blocks (deeper POCs on higher ranks)" if weak else
-                                         "240 POCs of one sequence in contiguous pair blocks over "
-                                         "the ranks"),
-                   **({"rank_only": {"rank": rank, "of": world}} if args.rank_only is not None else {})},
         "roofline": roofline,
-        # SURVEY §8(d) companions: in-frame candidates (the rows the kernels
-        # predict; out-of-frame rows are logged with their initial cost) and the
-        # compulsory bytes (orig + ref frame + results per pair) over the step
-        "value_inframe": inframe_total / tmax,
-        "compulsory": {"bytes_per_step_all": compulsory_total / args.steps,
-                       "GBps": compulsory_total / tmax / 1e9 if tmax > 0 else 0.0},
         "gather": gather_rec,
-    }
-    result["native"] = native_record()
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity_sample"] = cpu_baseline(run, acc, ncps, W, H, modes)
     eng.close()
@@ -470,6 +517,38 @@ def main():
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60e6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path: str, run, prefix: str) -> None:
+    """--dump-outputs: the result buffers of `run`'s jobs as the last step left
+    them, rows in job / refIdx / mode order: <prefix>cost.npy (float64) and
+    <prefix>cpmv.npy (float32 [rows, 7]).  More rows than DUMP_BYTES holds: a
+    fixed, seeded sample of them, their indices in <prefix>rows.npy (float64)."""
+    from vame.engine import MODES
+    torch.cuda.synchronize()
+    bufs = [job[3][k] for job in run.jobs for k in sorted(job[3], key=lambda k: (k[0], MODES.index(k[1])))]
+    rows = sum(c.numel() for c, _ in bufs)
+    idx = None
+    keep = int(DUMP_BYTES // (8 + 7 * 4 + 8))  # per row: cost, cpmv, its index
+    if rows * (8 + 7 * 4) > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(rows, keep, replace=False))
+    cost, cpmv, off = [], [], 0
+    for c, p in bufs:
+        if idx is not None:
+            lo, hi = np.searchsorted(idx, (off, off + c.numel()))
+            sel = torch.from_numpy(idx[lo:hi] - off).to(c.device)
+            off += c.numel()
+            c, p = c[sel], p[sel]
+        cost.append(c.cpu().numpy())
+        cpmv.append(p.cpu().numpy())
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, prefix + "cost.npy"), np.concatenate(cost).astype(np.float64))
+    np.save(os.path.join(path, prefix + "cpmv.npy"), np.concatenate(cpmv).astype(np.float32))
+    if idx is not None:
+        np.save(os.path.join(path, prefix + "rows.npy"), idx.astype(np.float64))
 
 
 def native_record() -> dict:

@@ -11,7 +11,7 @@ Reads, under <prof_dir>:
   pmc_sq/                         one PMC pass: SQ_WAVES SQ_INSTS_VALU
                                   SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES ... GRBM_GUI_ACTIVE
   count.json                      profiles/count_preds.py (instrumentation build)
-Every pass runs bench.py --no-spans, so each kernel's dispatches are the
+Every pass runs bench.py --full --no-spans, so each kernel's dispatches are the
 step's batched launches only (no per-POC launches of other sizes mixed into the
 per-launch averages).
 

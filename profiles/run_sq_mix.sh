@@ -12,7 +12,7 @@ G2="SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_V
 i=1
 for G in "$G1" "$G2"; do
   timeout -s KILL 300 rocprofv3 --pmc $G --output-format csv -d $O/p$i -o run -- \
-      python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-spans --fs-frames 0 "$@" > $O/p$i.log 2>&1
+      python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-spans --fs-frames 0 "$@" > $O/p$i.log 2>&1
   rc=$?; echo "$TAG pass $i rc=$rc"
   [ $rc -eq 0 ] || exit $rc
   i=$((i + 1))

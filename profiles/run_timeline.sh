@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for s in "${SETS[@]}"; do
   name=${s%%:*}; vars=${s#*:}
   env ${vars//,/ } VAME_BENCH_KTIMING=0 timeout -k 10 ${TMO:-300} rocprofv3 --kernel-trace --output-format csv \
-      -d $O/trace_$name -o run -- python3 $R/bench.py --no-cpu-baseline --fs-frames 0 --no-spans --steps 100 --warmup 10 "$@" \
+      -d $O/trace_$name -o run -- python3 $R/bench.py --full --no-cpu-baseline --fs-frames 0 --no-spans --steps 100 --warmup 10 "$@" \
       > $O/tr_$name.json 2> $O/tr_$name.err || { tail -5 $O/tr_$name.err; exit 1; }
   T=$(find $O/trace_$name -name "*kernel_trace.csv" -print -quit)
   echo "== $name"

@@ -1,5 +1,5 @@
 """Where a bench step's time goes between kernels: from a rocprofv3 kernel
-trace of `bench.py --no-spans`, the GPU's busy time (union of the two kernels'
+trace of `bench.py --full --no-spans`, the GPU's busy time (union of the two kernels'
 dispatch intervals) against the span, over the last `--last` dispatch pairs
 (the timed steps), and the idle gaps at step boundaries.
     python profiles/step_gaps.py <kernel_trace.csv> [--last N]"""

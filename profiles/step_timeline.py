@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Average timeline of a bench step from a rocprofv3 kernel trace of
-`bench.py --no-spans` (VAME_BENCH_KTIMING=0): the last N steps' dispatches
+`bench.py --full --no-spans` (VAME_BENCH_KTIMING=0): the last N steps' dispatches
 (one of each kernel per step, steps in order: the call's streams join at its
 end), each kernel's start / end relative to the step's first dispatch.
     python profiles/step_timeline.py <kernel_trace.csv> [--last N]"""

@@ -104,7 +104,7 @@ def test_bench_forced_rccl_group():
     device_id=...), the device-tensor all_reduce of the timing and the
     dist.gather of the decision records into rank 0 all run through RCCL;
     rank 0 then recomputes its block and checks the gathered records."""
-    r = run_bench(["--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--fs-frames", "4"],
+    r = run_bench(["--full", "--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--fs-frames", "4"],
                   {"VAME_FORCE_PG": "1"}, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -141,11 +141,11 @@ def check_frame_shard(d, world, backend):
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("weak", ["streams", "sequence"])
 def test_bench_gpus2_launches_two_ranks(weak):
-    """`python bench.py --gpus 2 --config c2 --steps 3` with no launcher: two
+    """`python bench.py --gpus 2 --full --config c2 --steps 3` with no launcher: two
     ranks (gloo, one GPU), one JSON line from rank 0 with n_gpus 2, the world
     it ran in, and the gathered records byte-identical to rank 0's recompute
     (both weak-scaling forms: a sequence per rank, pair blocks of one)."""
-    r = run_bench(["--gpus", "2", "--config", "c2", "--steps", "3", "--warmup", "1",
+    r = run_bench(["--gpus", "2", "--full", "--config", "c2", "--steps", "3", "--warmup", "1",
                    "--no-cpu-baseline", "--weak", weak, "--fs-frames", "6" if weak == "streams" else "0"],
                   {"VAME_DIST_BACKEND": "gloo"}, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -187,7 +187,7 @@ def test_bench_under_torchrun():
         e.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(REPO, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "3",
+                        os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--config", "c2", "--steps", "3",
                         "--warmup", "1", "--no-cpu-baseline", "--fs-frames", "0"], env=e, capture_output=True, text=True,
                        timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -198,3 +198,31 @@ def test_bench_under_torchrun():
                                                "forced_pg": False}
     assert d["gather"]["check"]["byte_identical"] is True
     assert d["native"]["lib"].endswith("libvame.so")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the line holds
+    the contract fields and none of the --full records.  --dump-outputs writes
+    the last step's result buffers, every row of the c2 step, as float64 costs
+    and float32 CPMV rows holding the integers the kernels wrote."""
+    import numpy as np
+    r = run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                  timeout=100)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "CU-blocks/s" and d["higher_is_better"] is True and d["dtype"] == "int32"
+    for key in ("roofline", "step_ms", "gather", "frame_shard", "cpu_baseline", "parity_sample"):
+        assert key not in d
+    rows = d["config"]["rows_per_step_rank0"]
+    assert rows == 3 * 65475
+    cost, cpmv = np.load(tmp_path / "out" / "cost.npy"), np.load(tmp_path / "out" / "cpmv.npy")
+    assert sorted(os.listdir(tmp_path / "out")) == ["cost.npy", "cpmv.npy"]
+    assert cost.dtype == np.float64 and cost.shape == (rows,)
+    assert cpmv.dtype == np.float32 and cpmv.shape == (rows, 7)
+    assert np.isfinite(cost).all() and (cost == np.rint(cost)).all()
+    assert (cpmv == np.rint(cpmv)).all() and (np.abs(cpmv) < 2 ** 24).all()

@@ -132,6 +132,42 @@ int vame_affine_me_batch(vame_ctx* ctx, const vame_poc_job* jobs, int njobs, int
 int vame_pack_records(vame_ctx* ctx, const vame_poc_job* jobs, int njobs, int mode_mask, int32_t* slab,
                       long long words, int32_t* bad, void* stream);
 
+/* Affine motion compensation: the prediction and / or the cost of CPMVs the
+ * caller already has (a chosen CU's winner, merge or inherited candidates),
+ * computed exactly as one prediction step of the search computes them.
+ * A descriptor (12 int32, device memory) is a CU at frame position (x, y) of
+ * size w x h, predicted from frame refs[ref] with the CPMVs cp: cp.nCPs = 2 or
+ * 3 selects the 4- or 6-parameter model (LB is ignored for 2).  Every 4x4
+ * sub-block: sub-block MV and spread test, roundAndClipMv against the CU
+ * position, clamp-to-edge window, 6-tap filter with the reference's rounding
+ * and clipPel (aux_functions.cl:146-212, :90-101, affine.cl:254-326,
+ * aux_functions.cl:1096-1239); PROF as vame_set_prof sets it, where the search
+ * applies it (the spread test passes).
+ *   pred : W*H device frame or NULL: receives the samples of the valid
+ *          descriptors' CUs and nothing else (where two CUs overlap, a sample
+ *          holds the result of one of them)
+ *   cost : ncus int64 (device) or NULL: sum of satd_4x4 against `cur` over the
+ *          CU + floor(lambda * (bits + 2)), the search's cost with its zero
+ *          predictor and ruiBits = 2 (affine.cl:416-446); lambda = 0: the SATD
+ *   bad  : device int32, OR-ed with 1 when a descriptor is invalid
+ * At least one of pred and cost is given; cur may be NULL when cost is.
+ * A valid descriptor has w, h in {16, 32, 64, 128}; x, y >= 0 and multiples
+ * of 4; x + w <= W, y + h <= H; 0 <= ref < nrefs; nCPs in {2, 3}; every used
+ * CPMV component in [-2^17, 2^17 - 1] (the range the search clamps to).  An
+ * invalid one writes nothing to pred, gets cost 0, sets bit 0 of *bad and does
+ * not disturb the others.
+ * The descriptors are not read on the host; the call allocates and
+ * synchronizes nothing and runs on `stream` alone (never the side stream), so
+ * it can be captured into a hipGraph.  Its offset table is the context's:
+ * calls on one context must be ordered one after the other (one stream, or
+ * events between streams).  ncus <= VAME_MC_MAX_CUS; ncus = 0 is a no-op.
+ * Frames are 8-byte aligned (refs: 4).  Argument errors: VAME_E_INVALID. */
+typedef struct { int32_t x, y, w, h, ref; vame_cpmvs cp; } vame_mc_cu;
+enum { VAME_MC_MAX_CUS = 1 << 20 };
+int vame_affine_mc(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                   const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
+                   int32_t* bad, void* stream);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

@@ -26,6 +26,7 @@ using namespace vame;
 
 static_assert(sizeof(vame_cpmvs) == 28, "Cpmvs layout (typedef.h)");
 static_assert(sizeof(vame_cpmvs_dev) == 28, "Cpmvs layout (typedef.h)");
+static_assert(sizeof(vame_mc_cu) == sizeof(McCu) && VAME_MC_MAX_CUS == kMcMaxCus, "vame_mc_cu layout");
 
 static thread_local char g_hip_err[256] = "";
 
@@ -119,6 +120,10 @@ struct vame_ctx {
   struct PackSeg* dPackSegs = nullptr;
   size_t dPackCap = 0;
   hipEvent_t packEv = nullptr;  // after the last pack kernel (it read the device table)
+  // vame_affine_mc: the sub-block offsets of up to VAME_MC_MAX_CUS descriptors
+  // and the scan's block sums (kMcScratchWords int32, ~4 MB), allocated by
+  // vame_create so that a call allocates nothing
+  int32_t* mcScratch = nullptr;
 };
 
 // One segment of a record pack: the n records of one (POC, refIdx, PRED),
@@ -904,6 +909,7 @@ int vame_create(vame_ctx** out, int device, int width, int height) {
       c->valueSync = 0;  // events instead
     }
   }
+  if (e == hipSuccess) e = hipMalloc(&c->mcScratch, kMcScratchWords * sizeof(int32_t));
   if (e != hipSuccess) {
     snprintf(g_hip_err, sizeof(g_hip_err), "%s", hipGetErrorString(e));
     vame_destroy(c);
@@ -944,6 +950,7 @@ void vame_destroy(vame_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->syncWord) (void)hipFree(c->syncWord);
   if (c->dPackSegs) (void)hipFree(c->dPackSegs);
+  if (c->mcScratch) (void)hipFree(c->mcScratch);
   for (int k = 0; k < kTimingClasses; k++)
     for (auto& e : c->ev[k]) {
       (void)hipEventDestroy(e.first);
@@ -975,6 +982,39 @@ int vame_affine_me(vame_ctx* c, const uint16_t* ref, const uint16_t* cur, float 
   kp.pair[0].cpmv[mode] = reinterpret_cast<vame_cpmvs_dev*>(cpmvs);
   kp.prev[align] = reinterpret_cast<const vame_cpmvs_dev*>(prev);
   return launch(c, std::vector<KParams>{kp}, align == 0, align == 1, align == 0, (hipStream_t)stream);
+}
+
+int vame_affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                   const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
+                   int32_t* bad, void* stream) {
+  if (!c || !refs || nrefs < 1 || nrefs > 4 || ncus < 0 || ncus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
+  if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
+  // the kernel reads window rows as dwords and moves block rows as 8-byte words
+  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
+  McParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++) {
+    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
+    p.refs[r] = refs[r];
+  }
+  if (ncus == 0) return VAME_OK;
+  if (!cus) return VAME_E_INVALID;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cus = reinterpret_cast<const McCu*>(cus);
+  p.pred = pred;
+  p.cost = cost;
+  p.bad = bad;
+  p.offs = c->mcScratch;
+  p.blockSum = c->mcScratch + kMcMaxCus + 1;
+  p.ncus = ncus;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.lambda = lambda;
+  VAME_HIP(mc_launch(p, c->prof, (hipStream_t)stream));
+  return VAME_OK;
 }
 
 int vame_template_coverage(int half128, int align, int32_t* hits, int32_t* items3) {

@@ -19,7 +19,7 @@ EXPORTS = (
     "vame_log_writer_refs", "vame_read_frames_range", "vame_count_lines", "vame_read_frames_span",
     "vame_log_writer_set_deferred", "vame_log_writer_num_files", "vame_log_writer_file_name",
     "vame_log_writer_sizes", "vame_log_writer_flush_at", "vame_template_coverage", "vame_pack_records",
-    "vame_count_lines_ranges", "vame_set_max_pairs", "vame_get_max_pairs",
+    "vame_count_lines_ranges", "vame_set_max_pairs", "vame_get_max_pairs", "vame_affine_mc",
 )
 
 
@@ -54,6 +54,7 @@ def lib():
         L.vame_affine_me_poc.argtypes = [P, P, P, I, F, I, I, ctypes.POINTER(PocResult), P]
         L.vame_affine_me_batch.argtypes = [P, ctypes.POINTER(PocJob), I, I, I, P]
         L.vame_pack_records.argtypes = [P, ctypes.POINTER(PocJob), I, I, P, ctypes.c_longlong, P, P]
+        L.vame_affine_mc.argtypes = [P, P, P, I, P, I, F, P, P, P, P]
         L.vame_num_ctus.argtypes = [I, I]
         L.vame_cus_per_ctu.argtypes = [I]
         L.vame_num_groups.argtypes = [I]

@@ -208,6 +208,41 @@ class Engine:
                                       bad.data_ptr(), self._stream()))
         return slab
 
+    def affine_mc(self, cus: torch.Tensor, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
+                  pred: torch.Tensor | None = None, want_cost: bool = False):
+        """vame_affine_mc: predict and / or cost caller-given CPMVs exactly as
+        one prediction step of the search does.  cus: int32 [n, 12] on the
+        engine's device, columns x, y, w, h, ref, nCPs, LTx, LTy, RTx, RTy,
+        LBx, LBy (vame.mc.cus_from_result builds them from result arrays);
+        refs: 1..4 frames, indexed by the ref column.  pred: a frame that
+        receives the samples of the valid descriptors' CUs (other samples keep
+        their value), or None; want_cost: return int64 cost[n] = SATD against
+        `cur` + floor(lam * (bits + 2)).  Returns (pred, cost, bad): bad is an
+        int32 device scalar, 1 when a descriptor was invalid (such a descriptor
+        writes no sample and costs 0).  Asynchronous on the current stream."""
+        if (cus.dim() != 2 or cus.shape[1] != 12 or cus.dtype != torch.int32 or cus.device != self.device
+                or not cus.is_contiguous()):
+            raise ValueError(f"cus must be a contiguous int32 [n, 12] tensor on {self.device}")
+        if pred is None and not want_cost:
+            raise ValueError("affine_mc needs pred, want_cost or both")
+        refs = [self._frame(r) for r in refs]
+        if not 1 <= len(refs) <= 4:
+            raise ValueError("affine_mc takes 1..4 reference frames")
+        if want_cost:
+            if cur is None:
+                raise ValueError("want_cost needs cur")
+            cur = self._frame(cur)
+        if pred is not None and (pred.shape != (self.H, self.W) or pred.device != self.device
+                                 or pred.dtype not in (torch.int16, torch.uint16) or not pred.is_contiguous()):
+            raise ValueError(f"pred must be a contiguous ({self.H},{self.W}) int16/uint16 frame on {self.device}")
+        n = cus.shape[0]
+        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+        check(lib().vame_affine_mc(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs), _ptr(cus), n,
+                                   float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+        return pred, cost, bad
+
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to
         code one alignment only.  Returns {(refIdx, MODE): (cost, cpmv)}."""

@@ -168,6 +168,59 @@ int vame_affine_mc(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* re
                    const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
                    int32_t* bad, void* stream);
 
+/* vame_affine_mc on the first min(*ncus_dev, max_cus) descriptors, the count
+ * read on the device (a negative count is 0): descriptors and cost entries
+ * past it are neither read nor written.  The launches are sized from max_cus
+ * (<= VAME_MC_MAX_CUS; 0 is a no-op); every other guarantee of vame_affine_mc
+ * holds -- the partner of vame_partition, whose leaf count stays on the device. */
+int vame_affine_mc_dev(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_cu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                       uint16_t* pred, int64_t* cost, int32_t* bad, void* stream);
+
+/* CU partition decision: per CTU the cheapest tiling by candidate CUs of the
+ * search's results of one POC, under VVC-style binary and ternary splits, and
+ * for every leaf its best (refIdx, 2-CP | 3-CP) candidate; the leaves come out
+ * as descriptors for vame_affine_mc(_dev).  The rule:
+ *   node   a CTU-relative rectangle (x, y, w, h), w, h in {16, 32, 64, 128},
+ *          x, y multiples of 16, inside the CTU; at frame position (X, Y)
+ *   value  X >= W or Y >= H: 0, nothing emitted.  A 16x16 node crossing the
+ *          frame edge (the last 8 rows at 1080p): 0, a hole.  Else the first
+ *          minimum, under strict <, of leaf, BT-H, BT-V, TT-H, TT-V:
+ *   leaf   only a node wholly in the frame that is a candidate CU of a PRED in
+ *          pred_mask: min of cost[r][m][ctu*{201|284} + offset] over
+ *          r = 0..nrefs-1 (outer) and m = 2-CP, 3-CP (inner), first minimum
+ *   split  split_penalty + the children's values (top to bottom / left to
+ *          right): BT-H two (w, h/2), h >= 32; BT-V two (w/2, h), w >= 32;
+ *          TT-H (w, h/4) (w, h/2) (w, h/4), h >= 64; TT-V the same in x; the TT
+ *          splits only with a HALF PRED in the mask
+ * Half-aligned candidates at an odd multiple of 8 are no nodes and never leaves.
+ *   res        device pointers; entries of PREDs outside pred_mask may be NULL
+ *   pred_mask  bits of vame_pred_mask(); at least one FULL PRED (so that every
+ *              CTU has a tiling)
+ *   split_penalty  0 .. 2^40
+ *   cus        nCtus*64 descriptors: frame x, y, w, h, ref, cp = the chosen
+ *              row's CPMVs with nCPs = 2 or 3.  CTUs ascending, a CTU's leaves
+ *              in raster order of their top-left 16x16 block
+ *   rows       or NULL: the row's index in its PRED array (PRED = 2*align + nCPs - 2)
+ *   ncus       device int32: the total number of leaves; entries of cus / rows
+ *              at or past it are not written
+ *   ctu_info   or NULL, [nCtus][4]: first leaf, leaves, holes, splits
+ *   ctu_cost   or NULL, [nCtus]: the root's value (split penalties included)
+ *   block_cu   or NULL, [nCtus*64] at ctu*64 + (y/16)*8 + x/16: the index into
+ *              cus of the leaf that covers the block, or -1
+ * Reads nothing on the host, allocates and synchronizes nothing, runs on
+ * `stream` alone and can be captured.  Its scratch is the context's: calls on
+ * one context are ordered one after the other.  Argument errors (nrefs outside
+ * 1..4, no FULL bit, a NULL array of a PRED in the mask, a penalty outside the
+ * range, NULL cus / ncus): VAME_E_INVALID, nothing written. */
+int vame_partition(vame_ctx* ctx, const vame_poc_result* res, int nrefs, int pred_mask,
+                   int64_t split_penalty, vame_mc_cu* cus, int32_t* rows, int32_t* ncus,
+                   int32_t* ctu_info, int64_t* ctu_cost, int32_t* block_cu, void* stream);
+/* The rule's candidate map (no device work): slot ((lh*4 + lw)*8 + y/16)*8 + x/16,
+ * lw = log2(w/16), lh = log2(h/16), of table[1024] holds align*512 + the
+ * candidate's output offset (RETURN_STRIDE[group] + cuIdx), or -1. */
+int vame_partition_table(int32_t* table);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

@@ -124,6 +124,9 @@ struct vame_ctx {
   // and the scan's block sums (kMcScratchWords int32, ~4 MB), allocated by
   // vame_create so that a call allocates nothing
   int32_t* mcScratch = nullptr;
+  // vame_partition: per CTU the leaf count, the leaves by top-left block and
+  // the blocks' owners, handed from the decision kernel to the emitting one
+  int32_t* partScratch = nullptr;
 };
 
 // One segment of a record pack: the n records of one (POC, refIdx, PRED),
@@ -910,6 +913,7 @@ int vame_create(vame_ctx** out, int device, int width, int height) {
     }
   }
   if (e == hipSuccess) e = hipMalloc(&c->mcScratch, kMcScratchWords * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&c->partScratch, (size_t)nCtus * kPartScratchWords * sizeof(int32_t));
   if (e != hipSuccess) {
     snprintf(g_hip_err, sizeof(g_hip_err), "%s", hipGetErrorString(e));
     vame_destroy(c);
@@ -951,6 +955,7 @@ void vame_destroy(vame_ctx* c) {
   if (c->syncWord) (void)hipFree(c->syncWord);
   if (c->dPackSegs) (void)hipFree(c->dPackSegs);
   if (c->mcScratch) (void)hipFree(c->mcScratch);
+  if (c->partScratch) (void)hipFree(c->partScratch);
   for (int k = 0; k < kTimingClasses; k++)
     for (auto& e : c->ev[k]) {
       (void)hipEventDestroy(e.first);
@@ -984,9 +989,10 @@ int vame_affine_me(vame_ctx* c, const uint16_t* ref, const uint16_t* cur, float 
   return launch(c, std::vector<KParams>{kp}, align == 0, align == 1, align == 0, (hipStream_t)stream);
 }
 
-int vame_affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
-                   const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
-                   int32_t* bad, void* stream) {
+// vame_affine_mc (ncus_dev NULL) and vame_affine_mc_dev (ncus = the capacity)
+static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                     const vame_mc_cu* cus, int ncus, const int32_t* ncus_dev, float lambda, uint16_t* pred,
+                     int64_t* cost, int32_t* bad, void* stream) {
   if (!c || !refs || nrefs < 1 || nrefs > 4 || ncus < 0 || ncus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
   if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
   // the kernel reads window rows as dwords and moves block rows as 8-byte words
@@ -1013,7 +1019,56 @@ int vame_affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs
   p.W = c->W;
   p.H = c->H;
   p.lambda = lambda;
+  p.ncusDev = ncus_dev;
   VAME_HIP(mc_launch(p, c->prof, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                   const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
+                   int32_t* bad, void* stream) {
+  return affine_mc(c, cur, refs, nrefs, cus, ncus, nullptr, lambda, pred, cost, bad, stream);
+}
+
+int vame_affine_mc_dev(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_cu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                       uint16_t* pred, int64_t* cost, int32_t* bad, void* stream) {
+  if (!ncus_dev) return VAME_E_INVALID;
+  return affine_mc(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, pred, cost, bad, stream);
+}
+
+int vame_partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty,
+                   vame_mc_cu* cus, int32_t* rows, int32_t* ncus, int32_t* ctu_info, int64_t* ctu_cost,
+                   int32_t* block_cu, void* stream) {
+  if (!c || !res || nrefs < 1 || nrefs > 4 || !cus || !ncus) return VAME_E_INVALID;
+  if ((pred_mask & ~15) || !(pred_mask & 3)) return VAME_E_INVALID;  // at least one FULL PRED
+  if (split_penalty < 0 || split_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
+  PartParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++)
+    for (int m = 0; m < 4; m++) {
+      if (!((pred_mask >> m) & 1)) continue;
+      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
+      p.cost[r][m] = res->cost[r][m];
+      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
+    }
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cus = reinterpret_cast<McCu*>(cus);
+  p.rows = rows;
+  p.ncus = ncus;
+  p.ctuInfo = ctu_info;
+  p.ctuCost = ctu_cost;
+  p.blockCu = block_cu;
+  p.scratch = c->partScratch;
+  p.penalty = split_penalty;
+  p.nrefs = nrefs;
+  p.predMask = pred_mask;
+  p.W = c->W;
+  p.H = c->H;
+  p.nCtus = c->nCtus;
+  p.ctusPerRow = c->ctusPerRow;
+  VAME_HIP(partition_launch(p, (hipStream_t)stream));
   return VAME_OK;
 }
 

@@ -2391,8 +2391,32 @@ struct McParams {
   int32_t* blockSum;        // [1024]: sub-blocks per scan block
   int ncus, nrefs, W, H;
   float lambda;
+  // vame_affine_mc_dev: the count lives on the device, clamped to [0, ncus]
+  // (ncus sizes the grids); NULL: the count is ncus
+  const int32_t* ncusDev;
 };
 // The three launches of one vame_affine_mc call on `stream` (ncus >= 1).
 hipError_t mc_launch(const McParams& p, bool prof, hipStream_t stream);
+
+// ------------------------------------------- partition decision (vame_partition.hip)
+constexpr int kPartSlots = 1024;  // nodes of a CTU: ((lh*4 + lw)*8 + y/16)*8 + x/16
+// int32 words of a context's scratch per CTU: the leaf count, the leaf code of
+// each of the 64 top-left blocks, the owner of each of the 64 blocks
+constexpr size_t kPartScratchWords = 1 + 64 + 64;
+struct PartParams {
+  const int64_t* cost[4][4];  // [refIdx][PRED], as vame_poc_result
+  const int32_t* cpmv[4][4];  // vame_cpmvs, 7 int32 per row
+  McCu* cus;
+  int32_t* rows;              // or NULL
+  int32_t* ncus;
+  int32_t* ctuInfo;           // or NULL
+  int64_t* ctuCost;           // or NULL
+  int32_t* blockCu;           // or NULL
+  int32_t* scratch;           // nCtus * kPartScratchWords
+  long long penalty;
+  int nrefs, predMask, W, H, nCtus, ctusPerRow;
+};
+// The two launches of one vame_partition call on `stream`.
+hipError_t partition_launch(const PartParams& p, hipStream_t stream);
 
 }  // namespace vame

@@ -16,6 +16,8 @@
 //                      scan of the counts inside blocks of 1024 descriptors
 //   mc_offsets_kernel  add the sum of the blocks before; the total goes to
 //                      offs[ncus]
+// (vame_affine_mc_dev: ncus is read from device memory by each kernel and
+// clamped to the capacity that sized the grids)
 //   mc_predict_kernel  grid-strided over the total (read from device memory);
 //                      a lane finds its CU by binary search in the offsets
 // Windows are read straight from the frame (filter_rows_global: aligned
@@ -61,12 +63,19 @@ __device__ __forceinline__ int block_scan_1024(int v, int* s_wave, int& total) {
 __device__ __forceinline__ bool mc_size_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
 __device__ __forceinline__ bool mc_mv_ok(int v) { return v >= kMvMin && v <= kMvMax; }
 
+// The descriptors of a call: p.ncus, or the device-side count of
+// vame_affine_mc_dev clamped to [0, p.ncus].
+__device__ __forceinline__ int mc_ncus(const McParams& p) {
+  return p.ncusDev ? min(max(*p.ncusDev, 0), p.ncus) : p.ncus;
+}
+
 __global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParams p) {
   __shared__ int s_wave[kMcScanBlock / 64];
   const int i = blockIdx.x * kMcScanBlock + threadIdx.x;
+  const int ncus = mc_ncus(p);
   int n = 0;
   bool flag = false;
-  if (i < p.ncus) {
+  if (i < ncus) {
     const McCu cu = p.cus[i];
     bool ok = mc_size_ok(cu.w) && mc_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 3) == 0;
     ok = ok && cu.x <= p.W - cu.w && cu.y <= p.H - cu.h;  // after the size test: no overflow
@@ -81,7 +90,7 @@ __global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParams p) {
   if (m && (int)__lane_id() == __builtin_ctzll(m)) atomicOr(p.bad, 1);
   int total;
   const int excl = block_scan_1024(n, s_wave, total);
-  if (i < p.ncus) p.offs[i] = excl;
+  if (i < ncus) p.offs[i] = excl;
   if (threadIdx.x == 0) p.blockSum[blockIdx.x] = total;
 }
 
@@ -90,11 +99,13 @@ __global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParams p) {
 __global__ __launch_bounds__(kMcScanBlock) void mc_offsets_kernel(McParams p) {
   __shared__ int s_wave[kMcScanBlock / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
+  const int ncus = mc_ncus(p);
   int base;
   block_scan_1024(tid < b ? p.blockSum[tid] : 0, s_wave, base);
   const int i = b * kMcScanBlock + tid;
-  if (i < p.ncus) p.offs[i] += base;
-  if (b == (int)gridDim.x - 1 && tid == 0) p.offs[p.ncus] = base + p.blockSum[b];
+  if (i < ncus) p.offs[i] += base;
+  // scan blocks past a device-side count hold no sub-blocks
+  if (b == (int)gridDim.x - 1 && tid == 0) p.offs[ncus] = base + p.blockSum[b];
 }
 
 // Sum over the 16 lanes of a DPP row, in every lane of the row.
@@ -119,11 +130,12 @@ __global__ __launch_bounds__(kMcThreads) void mc_predict_kernel(McParams p) {
   if (tid < 48) s_coef[tid] = reinterpret_cast<const uint4*>(&kCoefTab)[tid];
   __syncthreads();
   const int W = p.W, H = p.H;
-  const int total = p.offs[p.ncus];
+  const int ncus = mc_ncus(p);
+  const int total = p.offs[ncus];
   for (int g = blockIdx.x * kMcThreads + tid; g < total; g += (int)gridDim.x * kMcThreads) {
     // the last descriptor whose offset is <= g (descriptors without
     // sub-blocks share their successor's offset and are never found)
-    int lo = 0, hi = p.ncus;
+    int lo = 0, hi = ncus;
     while (hi - lo > 1) {
       const int mid = (lo + hi) >> 1;
       if (p.offs[mid] <= g)

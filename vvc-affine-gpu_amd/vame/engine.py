@@ -209,7 +209,7 @@ class Engine:
         return slab
 
     def affine_mc(self, cus: torch.Tensor, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
-                  pred: torch.Tensor | None = None, want_cost: bool = False):
+                  pred: torch.Tensor | None = None, want_cost: bool = False, ncus: torch.Tensor | None = None):
         """vame_affine_mc: predict and / or cost caller-given CPMVs exactly as
         one prediction step of the search does.  cus: int32 [n, 12] on the
         engine's device, columns x, y, w, h, ref, nCPs, LTx, LTy, RTx, RTy,
@@ -219,7 +219,10 @@ class Engine:
         their value), or None; want_cost: return int64 cost[n] = SATD against
         `cur` + floor(lam * (bits + 2)).  Returns (pred, cost, bad): bad is an
         int32 device scalar, 1 when a descriptor was invalid (such a descriptor
-        writes no sample and costs 0).  Asynchronous on the current stream."""
+        writes no sample and costs 0).  ncus: an int32 device scalar, the
+        number of descriptors to run (vame_affine_mc_dev: min(ncus, n), read on
+        the device; rows of cus and cost past it are neither read nor
+        written).  Asynchronous on the current stream."""
         if (cus.dim() != 2 or cus.shape[1] != 12 or cus.dtype != torch.int32 or cus.device != self.device
                 or not cus.is_contiguous()):
             raise ValueError(f"cus must be a contiguous int32 [n, 12] tensor on {self.device}")
@@ -239,9 +242,63 @@ class Engine:
         cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
         ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+        if ncus is not None:
+            if ncus.numel() != 1 or ncus.dtype != torch.int32 or ncus.device != self.device:
+                raise ValueError(f"ncus must be an int32 scalar on {self.device}")
+            check(lib().vame_affine_mc_dev(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs),
+                                           _ptr(cus), n, _ptr(ncus), float(lam), _ptr(pred), _ptr(cost), _ptr(bad),
+                                           self._stream()))
+            return pred, cost, bad
         check(lib().vame_affine_mc(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs), _ptr(cus), n,
                                    float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
         return pred, cost, bad
+
+    def partition(self, result: dict, preds: int | None = None, split_penalty: int = 0, out: dict | None = None):
+        """vame_partition: per CTU the cheapest tiling by the candidate CUs of
+        `result` (an alloc_poc dict of one POC, as the search filled it) under
+        binary and ternary splits, every leaf with its best (refIdx, 2-CP |
+        3-CP) candidate.  preds: the PREDs that take
+        part (bit m of MODES; None = every PRED the dict holds; at least one
+        FULL PRED); split_penalty: added per split, 0 .. 2^40.  Returns device
+        tensors: cus int32 [nCtus*64, 12] (descriptors for affine_mc; the
+        first ncus rows are written), rows int32 [nCtus*64] (the chosen row in
+        its PRED array), ncus int32 scalar, ctu_info int32 [nCtus, 4] (first,
+        count, holes, splits), ctu_cost int64 [nCtus], block_cu int32
+        [nCtus*64].  out: a dict of an earlier call to write into.  Reads
+        nothing on the host; asynchronous on the current stream."""
+        from . import partition as P
+        if not result:
+            raise ValueError("partition needs a result dict")
+        have = P.result_preds(result)
+        preds = have if preds is None else int(preds)
+        nrefs = max(r for r, _ in result) + 1
+        if preds & ~15 or not preds & 3:
+            raise ValueError("preds must hold a FULL PRED (bit 0 or 1) and only bits 0..3")
+        if not 0 <= int(split_penalty) <= P.MAX_PENALTY:
+            raise ValueError("split_penalty must be in [0, 2^40]")
+        for r in range(nrefs):
+            for m, name in enumerate(MODES):
+                if (preds >> m) & 1:
+                    if (r, name) not in result:
+                        raise ValueError(f"result buffers missing for {(r, name)}")
+                    self._check_out(result[(r, name)], m >> 1)
+        if out is not None:
+            want = P.alloc(0, "cpu")
+            for k in P.KEYS:
+                t = out[k]
+                shape = (self.n_ctus * 64, 12) if k == "cus" else (self.n_ctus, 4) if k == "ctu_info" else \
+                    () if k == "ncus" else (self.n_ctus,) if k == "ctu_cost" else (self.n_ctus * 64,)
+                if (tuple(t.shape) != shape or t.dtype != want[k].dtype or t.device != self.device
+                        or not t.is_contiguous()):
+                    raise ValueError(f"out[{k!r}] must be a contiguous {want[k].dtype} {shape} tensor on {self.device}")
+        return P.partition(self._h, self.n_ctus, self.device, result, preds, split_penalty, self._stream(), out)
+
+    def predict_partition(self, part: dict, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
+                          pred: torch.Tensor | None = None, want_cost: bool = False):
+        """affine_mc on the leaves of a partition() result, their count read on
+        the device: (pred, cost, bad) as affine_mc, cost int64 [nCtus*64] with
+        the first ncus entries written."""
+        return self.affine_mc(part["cus"], refs, lam, cur=cur, pred=pred, want_cost=want_cost, ncus=part["ncus"])
 
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to

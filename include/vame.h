@@ -221,6 +221,72 @@ int vame_partition(vame_ctx* ctx, const vame_poc_result* res, int nrefs, int pre
  * candidate's output offset (RETURN_STRIDE[group] + cuIdx), or -1. */
 int vame_partition_table(int32_t* table);
 
+/* ---- Affine bi-prediction: a CU predicted as the average of
+ * two hypotheses from two reference frames.  A hypothesis is one prediction of
+ * vame_affine_mc up to its second-stage accumulator acc = sum + 512 +
+ * (8192 << 6), whose uni sample is clip(acc >> 10); the bi sample is
+ *   clip((acc0 + acc1) >> 11, 0, 1023)
+ * (the unrounded values summed, one rounding; two identical hypotheses give
+ * the uni sample), and the bi cost the sum of satd_4x4 of the bi block against
+ * `cur` + floor(lambda * (bits(cp0) + bits(cp1) + 4)): each hypothesis carries
+ * its own ruiBits = 2.  PROF has no bi form: while vame_set_prof(ctx, 1) is in
+ * force the three calls return VAME_E_UNSUPPORTED and write nothing. */
+
+/* first 12 int32 are a vame_mc_cu; ref1 < 0: uni-predicted from (ref0, cp0) */
+typedef struct { int32_t x, y, w, h, ref0; vame_cpmvs cp0; int32_t ref1; vame_cpmvs cp1; } vame_mc_bicu; /* 80 B */
+
+/* vame_affine_mc_dev on bi descriptors: the first min(*ncus_dev, max_cus) of
+ * them (ncus_dev NULL: max_cus).  vame_affine_mc's validity rules hold per
+ * hypothesis; ref1 == -1 is the only negative value allowed (cp1 is then not
+ * read, samples and cost equal vame_affine_mc's bit for bit), ref1 == ref0 is
+ * allowed.  Every guarantee of vame_affine_mc(_dev) carries over: an invalid
+ * descriptor writes nothing, costs 0 and sets *bad; descriptors and costs at
+ * or past the count are untouched; nothing is read on the host, allocated or
+ * synchronized; `stream` alone, capturable; the context's offset table (calls
+ * on one context are ordered one after the other); max_cus <= VAME_MC_MAX_CUS. */
+int vame_affine_mc_bi(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                      const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                      uint16_t* pred, int64_t* cost, int32_t* bad, void* stream);
+
+/* The best reference pair of every candidate CU of the search's results `res`
+ * of one POC.  For every alignment a with a PRED in pred_mask and every row
+ * whose CU lies wholly in the frame: the hypothesis of refIdx r is the first
+ * minimum under strict < over m = 2-CP, 3-CP of cost[r][2a + m][row] among the
+ * PREDs in the mask, with that row's CPMVs; the candidates are the pairs
+ * r0 < r1 in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3);
+ *   bi_cost[a][row]  the first minimum of the bi cost over the pairs
+ *   bi_sel[a][row]   r0 + 4*m0 + 8*r1 + 32*m1 of that pair
+ * Rows of CUs that leave the frame get INT64_MAX and -1; with nrefs == 1 every
+ * row does.  bi_cost[a] / bi_sel[a]: nCtus*{201|284} entries (device), NULL
+ * allowed for an alignment without a PRED in the mask.  Every entry is written
+ * by the call's kernels (no host memset); integer sums: identical from run to
+ * run.  Reads nothing on the host, allocates and synchronizes nothing, runs on
+ * `stream` alone and can be captured; its scratch is the context's.  Argument
+ * errors (nrefs outside 1..4, an empty or unknown mask, a NULL array of a PRED
+ * in the mask, NULL outputs of an alignment in the mask): VAME_E_INVALID,
+ * nothing written. */
+int vame_bipred(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                const vame_poc_result* res, int pred_mask, int64_t* const bi_cost[2], int32_t* const bi_sel[2],
+                void* stream);
+
+/* vame_partition with a leaf that may be bi-predicted: the leaf value is the
+ * first minimum, under strict <, of the uni leaf minimum of vame_partition and
+ * bi_cost[a][row] + bi_penalty, the latter only where bi_sel[a][row] >= 0 (and
+ * names hypotheses the call holds: refIdx < nrefs, PREDs in pred_mask).
+ * Everything else is vame_partition's rule, word for word.
+ *   bi_cost, bi_sel  vame_bipred's outputs; needed for every alignment with a
+ *                    PRED in pred_mask
+ *   bi_penalty       0 .. 2^40
+ *   cus    nCtus*64 descriptors: a uni leaf is vame_partition's descriptor,
+ *          ref1 = -1 and a zero cp1; a bi leaf holds both hypotheses
+ *   rows   or NULL: the row inside its alignment's arrays
+ *   sel    or NULL: bi_sel of a bi leaf, -1 of a uni leaf
+ * ncus, ctu_info, ctu_cost, block_cu, the order of the leaves: vame_partition's. */
+int vame_partition_bi(vame_ctx* ctx, const vame_poc_result* res, int nrefs, int pred_mask,
+                      int64_t split_penalty, const int64_t* const bi_cost[2], const int32_t* const bi_sel[2],
+                      int64_t bi_penalty, vame_mc_bicu* cus, int32_t* rows, int32_t* sel, int32_t* ncus,
+                      int32_t* ctu_info, int64_t* ctu_cost, int32_t* block_cu, void* stream);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

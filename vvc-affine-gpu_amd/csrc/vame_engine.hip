@@ -15,6 +15,7 @@
 
 #include "../../include/vame.h"
 #include "vame_kernel.h"
+#include "vame_bipred.h"
 
 #if VAME_SPLIT_TU
 namespace vame {
@@ -27,6 +28,7 @@ using namespace vame;
 static_assert(sizeof(vame_cpmvs) == 28, "Cpmvs layout (typedef.h)");
 static_assert(sizeof(vame_cpmvs_dev) == 28, "Cpmvs layout (typedef.h)");
 static_assert(sizeof(vame_mc_cu) == sizeof(McCu) && VAME_MC_MAX_CUS == kMcMaxCus, "vame_mc_cu layout");
+static_assert(sizeof(vame_mc_bicu) == sizeof(McBiCu) && sizeof(McBiCu) == 80, "vame_mc_bicu layout");
 
 static thread_local char g_hip_err[256] = "";
 
@@ -127,6 +129,14 @@ struct vame_ctx {
   // vame_partition: per CTU the leaf count, the leaves by top-left block and
   // the blocks' owners, handed from the decision kernel to the emitting one
   int32_t* partScratch = nullptr;
+  // vame_bipred: the in-frame candidate CUs of the resolution (aligned first;
+  // biCands[0 .. biNCand[0]) aligned, then biNCand[1] half-aligned), the map
+  // group of 16 sub-blocks -> candidate (biNGroup[a] groups per alignment) and
+  // the pair SATD sums, 6 int64 per candidate
+  BiCand* biCands = nullptr;
+  int32_t* biGroupCand = nullptr;
+  int64_t* biPairSatd = nullptr;
+  int biNCand[2] = {0, 0}, biNGroup[2] = {0, 0};
 };
 
 // One segment of a record pack: the n records of one (POC, refIdx, PRED),
@@ -914,6 +924,42 @@ int vame_create(vame_ctx** out, int device, int width, int height) {
   }
   if (e == hipSuccess) e = hipMalloc(&c->mcScratch, kMcScratchWords * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc(&c->partScratch, (size_t)nCtus * kPartScratchWords * sizeof(int32_t));
+  if (e == hipSuccess) {  // vame_bipred's candidate tables
+    std::vector<BiCand> cands;
+    std::vector<int32_t> groupCand;
+    for (int align = 0; align < 2; align++) {
+      const int per = align ? kHalfCusPerCtu : kFullCusPerCtu;
+      for (int ctu = 0; ctu < nCtus; ctu++) {
+        const int X0 = (ctu % c->ctusPerRow) * kCtu, Y0 = (ctu / c->ctusPerRow) * kCtu;
+        for (int g = 0; g < (align ? kHalfGroups : kFullGroups); g++) {
+          int w, h, n, stride, xs[64], ys[64];
+          (void)vame_group_geometry(align, g, &w, &h, &n, &stride, xs, ys);
+          for (int k = 0; k < n; k++) {
+            const int x = X0 + xs[k], y = Y0 + ys[k];
+            if (x + w > width || y + h > height) continue;
+            int lw = 0, lh = 0;
+            while ((1 << lw) < w) lw++;
+            while ((1 << lh) < h) lh++;
+            BiCand cd;
+            cd.xy = x | (y << 16);
+            cd.shape = lw | (lh << 4) | (align << 8);
+            cd.row = ctu * per + stride + k;
+            cd.first = (int32_t)groupCand.size();
+            groupCand.insert(groupCand.end(), (size_t)(w * h) >> 8, (int32_t)cands.size());
+            cands.push_back(cd);
+          }
+        }
+      }
+      c->biNCand[align] = (int)cands.size() - (align ? c->biNCand[0] : 0);
+      c->biNGroup[align] = (int)groupCand.size() - (align ? c->biNGroup[0] : 0);
+    }
+    e = hipMalloc(&c->biCands, cands.size() * sizeof(BiCand));
+    if (e == hipSuccess) e = hipMemcpy(c->biCands, cands.data(), cands.size() * sizeof(BiCand), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&c->biGroupCand, groupCand.size() * sizeof(int32_t));
+    if (e == hipSuccess)
+      e = hipMemcpy(c->biGroupCand, groupCand.data(), groupCand.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&c->biPairSatd, cands.size() * kBiPairs * sizeof(int64_t));
+  }
   if (e != hipSuccess) {
     snprintf(g_hip_err, sizeof(g_hip_err), "%s", hipGetErrorString(e));
     vame_destroy(c);
@@ -956,6 +1002,9 @@ void vame_destroy(vame_ctx* c) {
   if (c->dPackSegs) (void)hipFree(c->dPackSegs);
   if (c->mcScratch) (void)hipFree(c->mcScratch);
   if (c->partScratch) (void)hipFree(c->partScratch);
+  if (c->biCands) (void)hipFree(c->biCands);
+  if (c->biGroupCand) (void)hipFree(c->biGroupCand);
+  if (c->biPairSatd) (void)hipFree(c->biPairSatd);
   for (int k = 0; k < kTimingClasses; k++)
     for (auto& e : c->ev[k]) {
       (void)hipEventDestroy(e.first);
@@ -1069,6 +1118,133 @@ int vame_partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_
   p.nCtus = c->nCtus;
   p.ctusPerRow = c->ctusPerRow;
   VAME_HIP(partition_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_affine_mc_bi(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                      const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                      uint16_t* pred, int64_t* cost, int32_t* bad, void* stream) {
+  if (!c || !refs || nrefs < 1 || nrefs > 4 || max_cus < 0 || max_cus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
+  if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
+  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
+  McBiParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++) {
+    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
+    p.refs[r] = refs[r];
+  }
+  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
+  if (max_cus == 0) return VAME_OK;
+  if (!cus) return VAME_E_INVALID;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cus = reinterpret_cast<const McBiCu*>(cus);
+  p.pred = pred;
+  p.cost = cost;
+  p.bad = bad;
+  p.offs = c->mcScratch;
+  p.blockSum = c->mcScratch + kMcMaxCus + 1;
+  p.ncus = max_cus;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.lambda = lambda;
+  p.ncusDev = ncus_dev;
+  VAME_HIP(mc_bi_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_bipred(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                const vame_poc_result* res, int pred_mask, int64_t* const bi_cost[2], int32_t* const bi_sel[2],
+                void* stream) {
+  if (!c || !cur || !refs || !res || nrefs < 1 || nrefs > 4 || !bi_cost || !bi_sel) return VAME_E_INVALID;
+  if ((pred_mask & ~15) || !pred_mask) return VAME_E_INVALID;
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  BiRowsParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++) {
+    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
+    p.refs[r] = refs[r];
+    for (int m = 0; m < 4; m++) {
+      if (!((pred_mask >> m) & 1)) continue;
+      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
+      p.cost[r][m] = res->cost[r][m];
+      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
+    }
+  }
+  const bool on[2] = {(pred_mask & 3) != 0, (pred_mask & 12) != 0};
+  for (int a = 0; a < 2; a++) {
+    if (!on[a]) continue;
+    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
+    p.biCost[a] = bi_cost[a];
+    p.biSel[a] = bi_sel[a];
+  }
+  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cands = c->biCands;
+  p.groupCand = c->biGroupCand;
+  p.pairSatd = c->biPairSatd;
+  p.candBegin = on[0] ? 0 : c->biNCand[0];
+  p.candEnd = on[1] ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
+  p.groupBegin = on[0] ? 0 : c->biNGroup[0];
+  p.groupEnd = on[1] ? c->biNGroup[0] + c->biNGroup[1] : c->biNGroup[0];
+  p.rowsOf[0] = c->nCtus * kFullCusPerCtu;
+  p.rowsOf[1] = c->nCtus * kHalfCusPerCtu;
+  p.nrefs = nrefs;
+  p.predMask = pred_mask;
+  p.W = c->W;
+  p.H = c->H;
+  p.lambda = lambda;
+  VAME_HIP(bipred_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_partition_bi(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty,
+                      const int64_t* const bi_cost[2], const int32_t* const bi_sel[2], int64_t bi_penalty,
+                      vame_mc_bicu* cus, int32_t* rows, int32_t* sel, int32_t* ncus, int32_t* ctu_info,
+                      int64_t* ctu_cost, int32_t* block_cu, void* stream) {
+  if (!c || !res || nrefs < 1 || nrefs > 4 || !cus || !ncus || !bi_cost || !bi_sel) return VAME_E_INVALID;
+  if ((pred_mask & ~15) || !(pred_mask & 3)) return VAME_E_INVALID;  // at least one FULL PRED
+  if (split_penalty < 0 || split_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
+  if (bi_penalty < 0 || bi_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
+  PartParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++)
+    for (int m = 0; m < 4; m++) {
+      if (!((pred_mask >> m) & 1)) continue;
+      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
+      p.cost[r][m] = res->cost[r][m];
+      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
+    }
+  for (int a = 0; a < 2; a++) {
+    if (!((pred_mask >> (2 * a)) & 3)) continue;
+    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
+    p.biCost[a] = bi_cost[a];
+    p.biSel[a] = bi_sel[a];
+  }
+  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cus = reinterpret_cast<McCu*>(cus);
+  p.rows = rows;
+  p.sel = sel;
+  p.ncus = ncus;
+  p.ctuInfo = ctu_info;
+  p.ctuCost = ctu_cost;
+  p.blockCu = block_cu;
+  p.scratch = c->partScratch;
+  p.penalty = split_penalty;
+  p.biPenalty = bi_penalty;
+  p.nrefs = nrefs;
+  p.predMask = pred_mask;
+  p.W = c->W;
+  p.H = c->H;
+  p.nCtus = c->nCtus;
+  p.ctusPerRow = c->ctusPerRow;
+  VAME_HIP(partition_launch(p, (hipStream_t)stream, true));
   return VAME_OK;
 }
 

@@ -2415,8 +2415,16 @@ struct PartParams {
   int32_t* scratch;           // nCtus * kPartScratchWords
   long long penalty;
   int nrefs, predMask, W, H, nCtus, ctusPerRow;
+  // vame_partition_bi only: the bi cost / selection of every row per alignment
+  // (vame_bipred's outputs), the penalty of a bi leaf; `cus` then holds 20-word
+  // vame_mc_bicu descriptors, `sel` (or NULL) each leaf's bi_sel or -1
+  const int64_t* biCost[2];
+  const int32_t* biSel[2];
+  long long biPenalty;
+  int32_t* sel;
 };
-// The two launches of one vame_partition call on `stream`.
-hipError_t partition_launch(const PartParams& p, hipStream_t stream);
+// The two launches of one vame_partition call on `stream`; bi: of one
+// vame_partition_bi call (the leaf may be a bi-predicted one).
+hipError_t partition_launch(const PartParams& p, hipStream_t stream, bool bi = false);
 
 }  // namespace vame

@@ -23,6 +23,10 @@
 //   part_emit_kernel    one wave per CTU: the sum of the counts before it,
 //                       each leaf's place by ballot + popcount over the 64
 //                       blocks, the descriptors with the chosen row's CPMVs
+// Both kernels are templates on BI: <false> is vame_partition; <true> is
+// vame_partition_bi, whose leaf may be the row's bi-predicted
+// candidate (vame_bipred's bi_cost + bi_penalty) and whose descriptors are the
+// 20-word vame_mc_bicu.
 #include <hip/hip_runtime.h>
 
 #include "../../include/vame.h"
@@ -77,10 +81,14 @@ __device__ __forceinline__ long long part_add(long long a, long long b) {
   return (a == kPartInf || b == kPartInf) ? kPartInf : a + b;
 }
 
+// BI (vame_partition_bi): the leaf value is the first minimum of the uni leaf
+// minimum and bi_cost + bi_penalty, the latter only where bi_sel names two
+// hypotheses the call holds (refIdx < nrefs, PREDs in the mask).
+template <bool BI>
 __global__ __launch_bounds__(kPartThreads) void part_decide_kernel(PartParams p) {
   __shared__ long long s_val[kPartSlots];
   __shared__ unsigned char s_dec[kPartSlots];
-  __shared__ unsigned char s_sel[kPartSlots];   // leaf: refIdx | (nCPs - 2) << 2
+  __shared__ unsigned char s_sel[kPartSlots];   // leaf: refIdx | (nCPs - 2) << 2; bit 7: a bi leaf
   __shared__ unsigned char s_mark[kPartSlots];
   __shared__ int s_leaf[64];                    // by top-left block: the leaf's code, or -1
   __shared__ int s_owner[64];                   // by block: the top-left block of its leaf, or -1
@@ -130,6 +138,19 @@ __global__ __launch_bounds__(kPartThreads) void part_decide_kernel(PartParams p)
                 dec = kDecLeaf;
               }
             }
+          if (BI) {
+            const int s = p.biSel[align][row];
+            const int pm = (p.predMask >> (2 * align)) & 3;
+            if (s >= 0 && s < 64 && (s & 3) < p.nrefs && ((s >> 3) & 3) < p.nrefs && ((pm >> ((s >> 2) & 1)) & 1) &&
+                ((pm >> ((s >> 5) & 1)) & 1)) {
+              const long long c = p.biCost[align][row] + p.biPenalty;
+              if (c < best) {
+                best = c;
+                sel = 0x80;
+                dec = kDecLeaf;
+              }
+            }
+          }
         }
       }
     }
@@ -248,6 +269,7 @@ __global__ __launch_bounds__(kPartThreads) void part_decide_kernel(PartParams p)
   }
 }
 
+template <bool BI>
 __global__ __launch_bounds__(64) void part_emit_kernel(PartParams p) {
   const int lane = threadIdx.x, ctu = blockIdx.x;
   // the leaves of the CTUs before this one (at most 510 counts)
@@ -261,10 +283,12 @@ __global__ __launch_bounds__(64) void part_emit_kernel(PartParams p) {
   const unsigned long long leaves = __builtin_amdgcn_ballot_w64(code >= 0);
   if (code >= 0) {
     const int idx = first + __popcll(leaves & ((1ull << lane) - 1));
-    const int slot = code & 1023, r = (code >> 10) & 3, m = (code >> 12) & 1;
+    const int slot = code & 1023;
     const int e = kPartTable.v[slot];
     const int align = e >> 9;
     const int row = ctu * (align ? kHalfCusPerCtu : kFullCusPerCtu) + (e & 511);
+    const int bsel = BI && ((code >> 17) & 1) ? p.biSel[align][row] : -1;
+    const int r = bsel >= 0 ? bsel & 3 : (code >> 10) & 3, m = bsel >= 0 ? (bsel >> 2) & 1 : (code >> 12) & 1;
     const int32_t* cp = p.cpmv[r][2 * align + m] + (size_t)row * 7;
     McCu cu;
     cu.x = (ctu % p.ctusPerRow) * kCtu + (slot & 7) * 16;
@@ -274,7 +298,25 @@ __global__ __launch_bounds__(64) void part_emit_kernel(PartParams p) {
     cu.ref = r;
     cu.ncps = 2 + m;
     cu.ltx = cp[1]; cu.lty = cp[2]; cu.rtx = cp[3]; cu.rty = cp[4]; cu.lbx = cp[5]; cu.lby = cp[6];
-    p.cus[idx] = cu;
+    if (BI) {
+      int32_t* d = reinterpret_cast<int32_t*>(p.cus) + (size_t)idx * 20;
+      *reinterpret_cast<McCu*>(d) = cu;
+      if (bsel >= 0) {
+        const int r1 = (bsel >> 3) & 3, m1 = (bsel >> 5) & 1;
+        const int32_t* cp1 = p.cpmv[r1][2 * align + m1] + (size_t)row * 7;
+        d[12] = r1;
+        d[13] = 2 + m1;
+#pragma unroll
+        for (int k = 0; k < 6; k++) d[14 + k] = cp1[1 + k];
+      } else {
+        d[12] = -1;
+#pragma unroll
+        for (int k = 13; k < 20; k++) d[k] = 0;
+      }
+      if (p.sel) p.sel[idx] = bsel;
+    } else {
+      p.cus[idx] = cu;
+    }
     if (p.rows) p.rows[idx] = row;
   }
   if (p.blockCu)
@@ -285,9 +327,14 @@ __global__ __launch_bounds__(64) void part_emit_kernel(PartParams p) {
   }
 }
 
-hipError_t partition_launch(const PartParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL(part_decide_kernel, dim3(p.nCtus), dim3(kPartThreads), 0, stream, p);
-  hipLaunchKernelGGL(part_emit_kernel, dim3(p.nCtus), dim3(64), 0, stream, p);
+hipError_t partition_launch(const PartParams& p, hipStream_t stream, bool bi) {
+  if (bi) {
+    hipLaunchKernelGGL(part_decide_kernel<true>, dim3(p.nCtus), dim3(kPartThreads), 0, stream, p);
+    hipLaunchKernelGGL(part_emit_kernel<true>, dim3(p.nCtus), dim3(64), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL(part_decide_kernel<false>, dim3(p.nCtus), dim3(kPartThreads), 0, stream, p);
+    hipLaunchKernelGGL(part_emit_kernel<false>, dim3(p.nCtus), dim3(64), 0, stream, p);
+  }
   return hipGetLastError();
 }
 

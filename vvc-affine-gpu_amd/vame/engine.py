@@ -298,7 +298,148 @@ class Engine:
         """affine_mc on the leaves of a partition() result, their count read on
         the device: (pred, cost, bad) as affine_mc, cost int64 [nCtus*64] with
         the first ncus entries written."""
+        if part["cus"].dim() == 2 and part["cus"].shape[1] == 20:  # a partition_bi() result
+            return self.affine_mc_bi(part["cus"], refs, lam, cur=cur, pred=pred, want_cost=want_cost,
+                                     ncus=part["ncus"])
         return self.affine_mc(part["cus"], refs, lam, cur=cur, pred=pred, want_cost=want_cost, ncus=part["ncus"])
+
+    # ---- bi-prediction (DESIGN.md section 13)
+    def _check_result(self, result: dict, preds: int, what: str):
+        """An alloc_poc dict that holds every PRED of `preds` for refIdx
+        0 .. nrefs-1: (nrefs, its vame_poc_result)."""
+        if not result:
+            raise ValueError(f"{what} needs a result dict")
+        nrefs = max(r for r, _ in result) + 1
+        if not 1 <= nrefs <= 4:
+            raise ValueError(f"{what} takes the results of 1..4 references")
+        pr = PocResult()
+        for r in range(nrefs):
+            for m, name in enumerate(MODES):
+                if (preds >> m) & 1:
+                    if (r, name) not in result:
+                        raise ValueError(f"result buffers missing for {(r, name)}")
+                    cost, cpmv = self._check_out(result[(r, name)], m >> 1)
+                    pr.cost[r][m] = cost.data_ptr()
+                    pr.cpmvs[r][m] = cpmv.data_ptr()
+        return nrefs, pr
+
+    def _check_bi(self, bi: dict, preds: int):
+        """vame_bipred's arrays of the alignments in `preds`: two 2-pointer arrays."""
+        V = ctypes.c_void_p
+        cost, sel = (V * 2)(), (V * 2)()
+        for a in (0, 1):
+            if not (preds >> (2 * a)) & 3:
+                continue
+            try:
+                c, s = bi["cost"][a], bi["sel"][a]
+            except (KeyError, IndexError, TypeError):
+                c = s = None
+            n = self.n_cus(a)
+            if (c is None or s is None or c.dtype != torch.int64 or s.dtype != torch.int32 or c.numel() != n
+                    or s.numel() != n or c.device != self.device or s.device != self.device
+                    or not c.is_contiguous() or not s.is_contiguous()):
+                raise ValueError(f"bi['cost'][{a}] / bi['sel'][{a}] must be contiguous int64[{n}] / int32[{n}] "
+                                 f"on {self.device}")
+            cost[a], sel[a] = c.data_ptr(), s.data_ptr()
+        return cost, sel
+
+    def affine_mc_bi(self, cus: torch.Tensor, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
+                     pred: torch.Tensor | None = None, want_cost: bool = False, ncus: torch.Tensor | None = None):
+        """vame_affine_mc_bi: affine_mc on bi descriptors, int32 [n, 20] with
+        the columns vame.bipred.BICU_FIELDS: a 12-column descriptor, then ref1
+        and the second hypothesis' nCPs and CPMVs.  ref1 = -1: uni-predicted,
+        exactly affine_mc; else the sample is the once-rounded average of the
+        two hypotheses and the cost carries both rates.  Arguments and the
+        returned (pred, cost, bad) as affine_mc.  Not available under PROF."""
+        if (cus.dim() != 2 or cus.shape[1] != 20 or cus.dtype != torch.int32 or cus.device != self.device
+                or not cus.is_contiguous()):
+            raise ValueError(f"cus must be a contiguous int32 [n, 20] tensor on {self.device}")
+        if pred is None and not want_cost:
+            raise ValueError("affine_mc_bi needs pred, want_cost or both")
+        refs = [self._frame(r) for r in refs]
+        if not 1 <= len(refs) <= 4:
+            raise ValueError("affine_mc_bi takes 1..4 reference frames")
+        if want_cost:
+            if cur is None:
+                raise ValueError("want_cost needs cur")
+            cur = self._frame(cur)
+        if pred is not None and (pred.shape != (self.H, self.W) or pred.device != self.device
+                                 or pred.dtype not in (torch.int16, torch.uint16) or not pred.is_contiguous()):
+            raise ValueError(f"pred must be a contiguous ({self.H},{self.W}) int16/uint16 frame on {self.device}")
+        if ncus is not None and (ncus.numel() != 1 or ncus.dtype != torch.int32 or ncus.device != self.device):
+            raise ValueError(f"ncus must be an int32 scalar on {self.device}")
+        n = cus.shape[0]
+        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+        check(lib().vame_affine_mc_bi(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs), _ptr(cus), n,
+                                      _ptr(ncus), float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+        return pred, cost, bad
+
+    def bipred(self, cur, refs, lam: float, result: dict, preds: int | None = None, out: dict | None = None):
+        """vame_bipred: for every candidate CU of `result` (an alloc_poc dict
+        of one POC over the frames `refs`) the cheapest pair of two references'
+        winners.  Returns {"cost": [FULL, HALF], "sel": [FULL, HALF]}: int64 /
+        int32 arrays over the rows of each alignment (None for an alignment
+        without a PRED in `preds`); rows of CUs that leave the frame, and every
+        row with one reference, hold INT64_MAX and -1; sel = r0 + 4*m0 + 8*r1 +
+        32*m1 (vame.bipred.decode_sel).  preds: None = every PRED the dict
+        holds.  out: a dict of an earlier call to write into."""
+        from . import bipred as B
+        from . import partition as P
+        cur = self._frame(cur)
+        refs = [self._frame(r) for r in refs]
+        if not 1 <= len(refs) <= 4:
+            raise ValueError("bipred takes 1..4 reference frames")
+        if not result:
+            raise ValueError("bipred needs a result dict")
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds:
+            raise ValueError("preds must hold a PRED and only bits 0..3")
+        nrefs, pr = self._check_result(result, preds, "bipred")
+        if nrefs != len(refs):
+            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
+        if out is None:
+            full = B.alloc_bi(self.n_ctus, self.device)
+            out = {k: [t if (preds >> (2 * a)) & 3 else None for a, t in enumerate(full[k])] for k in ("cost", "sel")}
+        cost, sel = self._check_bi(out, preds)
+        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+        check(lib().vame_bipred(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds,
+                                cost, sel, self._stream()))
+        return out
+
+    def partition_bi(self, result: dict, bi: dict, preds: int | None = None, split_penalty: int = 0,
+                     bi_penalty: int = 0, out: dict | None = None):
+        """vame_partition_bi: partition() whose leaves may be bi-predicted: a
+        leaf's value is the smaller of its uni minimum and bi cost + bi_penalty
+        (bi: a bipred() result over the same `result`).  Returns the tensors of
+        partition() with cus int32 [nCtus*64, 20] (vame.bipred.BICU_FIELDS;
+        ref1 = -1 for a uni leaf) and sel int32 [nCtus*64] (bi_sel, or -1)."""
+        from . import bipred as B
+        from . import partition as P
+        if not result:
+            raise ValueError("partition_bi needs a result dict")
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds & 3:
+            raise ValueError("preds must hold a FULL PRED (bit 0 or 1) and only bits 0..3")
+        if not 0 <= int(split_penalty) <= B.MAX_PENALTY or not 0 <= int(bi_penalty) <= B.MAX_PENALTY:
+            raise ValueError("split_penalty and bi_penalty must be in [0, 2^40]")
+        nrefs, pr = self._check_result(result, preds, "partition_bi")
+        bcost, bsel = self._check_bi(bi, preds)
+        want = B.alloc(0, "cpu")
+        if out is None:
+            out = B.alloc(self.n_ctus, self.device)
+        for k in B.KEYS:
+            t = out[k]
+            shape = (self.n_ctus * 64, 20) if k == "cus" else (self.n_ctus, 4) if k == "ctu_info" else \
+                () if k == "ncus" else (self.n_ctus,) if k == "ctu_cost" else (self.n_ctus * 64,)
+            if (tuple(t.shape) != shape or t.dtype != want[k].dtype or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"out[{k!r}] must be a contiguous {want[k].dtype} {shape} tensor on {self.device}")
+        V = ctypes.c_void_p
+        check(lib().vame_partition_bi(self._h, ctypes.byref(pr), nrefs, preds, int(split_penalty), bcost, bsel,
+                                      int(bi_penalty), *(V(out[k].data_ptr()) for k in B.KEYS), self._stream()))
+        return out
 
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to

@@ -31,8 +31,8 @@ KFLAGS     := -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-
 KFLAGS_2CP := -mllvm -simplifycfg-sink-common=false -mllvm -simplifycfg-hoist-common=false \
               -mllvm -structurizecfg-skip-uniform-regions=true
 
-LIB_SRCS := $(CSRC)/vame_engine.hip $(CSRC)/vame_kernels_2cp.hip $(CSRC)/vame_mc.hip $(CSRC)/vame_partition.hip $(CSRC)/vame_bipred.hip $(CSRC)/vame_hostlogic.cpp $(CSRC)/vame_io.cpp
-LIB_HDRS := $(CSRC)/vame_kernel.h $(CSRC)/vame_bipred.h $(CSRC)/vame_tables.h include/vame.h
+LIB_SRCS := $(CSRC)/vame_engine.hip $(CSRC)/vame_kernels_2cp.hip $(CSRC)/vame_mc.hip $(CSRC)/vame_partition.hip $(CSRC)/vame_bipred.hip $(CSRC)/vame_birefine.hip $(CSRC)/vame_hostlogic.cpp $(CSRC)/vame_io.cpp
+LIB_HDRS := $(CSRC)/vame_kernel.h $(CSRC)/vame_bipred.h $(CSRC)/vame_birefine.h $(CSRC)/vame_tables.h include/vame.h
 OBJDIR   := $(PKG)/build
 # $(call build_lib,<output .so>,<extra flags>): every unit with its own flags, then one link
 define build_lib
@@ -42,11 +42,12 @@ define build_lib
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).mc.o $(CSRC)/vame_mc.hip
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).partition.o $(CSRC)/vame_partition.hip
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).bipred.o $(CSRC)/vame_bipred.hip
+	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).birefine.o $(CSRC)/vame_birefine.hip
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).hostlogic.o $(CSRC)/vame_hostlogic.cpp
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).io.o $(CSRC)/vame_io.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $(1) $(OBJDIR)/$(notdir $(1)).engine.o \
 	    $(OBJDIR)/$(notdir $(1)).2cp.o $(OBJDIR)/$(notdir $(1)).mc.o $(OBJDIR)/$(notdir $(1)).partition.o \
-	    $(OBJDIR)/$(notdir $(1)).bipred.o $(OBJDIR)/$(notdir $(1)).hostlogic.o $(OBJDIR)/$(notdir $(1)).io.o
+	    $(OBJDIR)/$(notdir $(1)).bipred.o $(OBJDIR)/$(notdir $(1)).birefine.o $(OBJDIR)/$(notdir $(1)).hostlogic.o $(OBJDIR)/$(notdir $(1)).io.o
 endef
 
 all: lib cli synth oracle probe
@@ -99,6 +100,7 @@ resource-usage:
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_mc.hip
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_partition.hip
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_bipred.hip
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_birefine.hip
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(OBJDIR)

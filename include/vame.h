@@ -287,6 +287,43 @@ int vame_partition_bi(vame_ctx* ctx, const vame_poc_result* res, int nrefs, int 
                       int64_t bi_penalty, vame_mc_bicu* cus, int32_t* rows, int32_t* sel, int32_t* ncus,
                       int32_t* ctu_info, int64_t* ctu_cost, int32_t* block_cu, void* stream);
 
+/* Refinement of bi-predicted CUs: one hypothesis is held, the
+ * other re-estimated against what the held one leaves to explain, then the
+ * roles swap.  Works on the first min(*ncus_dev, max_cus) descriptors
+ * (ncus_dev NULL: max_cus; a negative count is 0); entries of cus, out and
+ * cost at or past the count are neither read nor written.
+ * A valid bi descriptor (vame_affine_mc_bi's rules, ref1 >= 0, ref1 == ref0
+ * allowed): out[i] is the descriptor with its refined CPMVs and cost[i] its bi
+ * cost, bit for bit vame_affine_mc_bi's cost of out[i].  The rule is the
+ * search's iteration (oracle/vame_oracle.c:run_cu) with two references:
+ *   state   best = (cp0, cp1) as given, bestCost = the bi cost of the input
+ *   round   t = 0 .. rounds-1 moves hypothesis m = 1 - (t & 1) and holds
+ *           f = 1 - m; both start at best.  acc_f and P_f = clip(acc_f >> 10)
+ *           are taken once per round.  The moving hypothesis runs the search's
+ *           loop with its own nCPs, niter = 5 (2-CP) or 4 (3-CP); for it =
+ *           0 .. niter: predict it as vame_affine_mc does (acc_m, P_m); the
+ *           bi cost of (curr, best[f]); under strict < against bestCost take
+ *           curr as best[m]; unless it == niter, one gradient step on P_m --
+ *           Sobel gradients, normal equations, solveEqual, scaleDeltaMvs, the
+ *           wrapping add, clamp to +-2^17 and clipMv -- with the error term
+ *           e = 2 cur - P_f - P_m.  A 2-CP hypothesis never changes its LB.
+ *   rounds  0 .. 4; 0 copies the descriptors and returns their costs
+ * The cost never rises.  A uni descriptor (ref1 == -1) is copied through with
+ * its uni cost; an invalid one is copied through, costs 0 and ORs 1 into *bad.
+ * out may be cus; cost holds max_cus entries.  All sums are integer or run in
+ * solveEqual's fixed order: identical from run to run.
+ * Reads nothing on the host, allocates and synchronizes nothing, runs on
+ * `stream` alone and can be captured.  It uses no scratch of the context:
+ * calls on one context need no ordering among themselves.  Frames are 8-byte
+ * aligned (refs: 4).  While vame_set_prof(ctx, 1) is in force:
+ * VAME_E_UNSUPPORTED, nothing written.  Argument errors (NULL cur, refs, cus,
+ * out, cost or bad; nrefs outside 1..4; rounds outside 0..4; max_cus outside
+ * 0..VAME_MC_MAX_CUS; a misaligned frame): VAME_E_INVALID, nothing written.
+ * max_cus = 0 is a no-op. */
+int vame_bipred_refine(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                       int rounds, vame_mc_bicu* out, int64_t* cost, int32_t* bad, void* stream);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

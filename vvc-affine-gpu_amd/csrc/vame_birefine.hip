@@ -1,0 +1,351 @@
+// vame_birefine.hip -- refinement of bi-predicted CUs (vame_bipred_refine,
+// include/vame.h): one hypothesis of a bi descriptor is held,
+// the other runs the search's gradient iteration against what the held one
+// leaves to explain, e = 2 cur - P_fixed - P_moving; then the roles swap.
+//
+// Work mapping: one workgroup per descriptor, one lane per 4x4 sub-block, in
+// three size classes -- 64, 256 and 1024 lanes for CUs of up to 64, 256 and
+// 1024 sub-blocks.  The count of descriptors lives on the device, so every
+// class is launched over the whole capacity and a workgroup whose descriptor
+// is past the count or of another class leaves at once.  Per lane, in
+// registers: the original block, the fixed hypothesis' 16 accumulators and
+// 2 cur - P_fixed; in LDS: the moving hypothesis' samples P_m as int16 [h][w]
+// (2 / 8 / 32 KB) for the Sobel neighbourhood, the 24 int64 moments and the
+// 6x7 FP64 system.  Every step of the iteration is the search's device
+// function (vame_kernel.h): mv_field, filter_rows_global, satd_4x4, grad_sb,
+// eq_value, seg_solve, scale_delta; only the loop around them is new.
+//
+// Operand widths with |e| <= 2046 (the search has |e| <= 1023): e and
+// 2 cur - P_fixed (-1023 .. 2046) fit the packed int16 lanes of grad_sb; its
+// five sums over 16 samples stay below 16 * 4092^2 < 2^29; eq_value
+// multiplies them by monomials <= 126^2 in int64 (< 2^43 per sub-block,
+// < 2^53 per CU); the right-hand side's * 8 happens in FP64 (exact).
+#include <hip/hip_runtime.h>
+
+#include "vame_birefine.h"
+#include "vame_kernel.h"
+
+namespace vame {
+
+static_assert(sizeof(McBiCu) == 80, "vame_mc_bicu layout");
+static_assert(kNumVal2 <= kNumMom, "one moment table for both models");
+
+__device__ __forceinline__ bool br_size_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
+__device__ __forceinline__ bool br_mv_ok(int v) { return v >= kMvMin && v <= kMvMax; }
+__device__ __forceinline__ bool br_cp_ok(int ncps, const int32_t (&c)[6]) {
+  bool ok = (ncps == 2 || ncps == 3) && br_mv_ok(c[0]) && br_mv_ok(c[1]) && br_mv_ok(c[2]) && br_mv_ok(c[3]);
+  if (ncps == 3) ok = ok && br_mv_ok(c[4]) && br_mv_ok(c[5]);
+  return ok;
+}
+
+// The second-stage accumulators of one hypothesis for the sub-block at (sx, sy)
+// of the CU (x, y, 2^lw, 2^lh): vame_affine_mc's prediction up to the rounding
+// shift.  Every load is clamped to the frame, whatever the CPMVs hold.
+__device__ __forceinline__ void br_hyp_acc(const uint16_t* __restrict__ ref, int x, int y, int lw, int lh,
+                                           const int (&cp)[6], int ncps, int sx, int sy, int W, int H,
+                                           const uint4* s_coef, int (&acc)[4][4]) {
+  const MvField f = mv_field(cp, ncps, lw, lh);
+  const int px = f.spread ? (1 << (lw - 1)) : sx + 2, py = f.spread ? (1 << (lh - 1)) : sy + 2;
+  int mx = f.bx + __mul24(f.hx, px) + __mul24(f.vx, py);
+  int my = f.by + __mul24(f.hy, px) + __mul24(f.vy, py);
+  mx = (mx + 64 - (mx >= 0)) >> 7;  // roundMv (aux_functions.cl:38-47)
+  my = (my + 64 - (my >= 0)) >> 7;
+  // clipMv (aux_functions.cl:51-67) on the frame position of the MV's target
+  const int ax = clampi(mx + shl(x, 4), -135 * 16, (W + 7) * 16);
+  const int ay = clampi(my + shl(y, 4), -135 * 16, (H + 7) * 16);
+  const int fx = ax & 15, fy = ay & 15;
+  const int wx = (ax >> 4) + sx - 2, wy = (ay >> 4) + sy - 2;  // window origin (frame)
+  const uint4 KA = s_coef[fx * 3], KB = s_coef[fx * 3 + 1];
+#pragma unroll
+  for (int r = 0; r < 4; r++)
+#pragma unroll
+    for (int c = 0; c < 4; c++) acc[r][c] = 524800;  // (1 << 9) + (8192 << 6)
+  filter_rows_global(ref, wx, wy, W, H, KA, KB, reinterpret_cast<const unsigned*>(s_coef), fy, acc);
+}
+
+// bi samples clampi((a + b) >> 11, 0, 1023), packed rows
+__device__ __forceinline__ void br_pack_bi(const int (&a)[4][4], const int (&b)[4][4], uint2 (&P)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    int s[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) s[c] = clampi((a[r][c] + b[r][c]) >> 11, 0, 1023);
+    P[r] = make_uint2(pack16(s[0], s[1]), pack16(s[2], s[3]));
+  }
+}
+
+__device__ __forceinline__ int br_wave_sum(int v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ long long br_wave_sum64(long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// Sum of `v` over the workgroup, in every lane (called by all of them).
+template <int NT>
+__device__ __forceinline__ long long br_block_sum(int v, unsigned long long* s_sum) {
+  v = br_wave_sum(v);
+  if constexpr (NT == 64) return v;
+  __syncthreads();  // the readers of the previous sum are done
+  if (threadIdx.x == 0) *s_sum = 0;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) atomicAdd(s_sum, (unsigned long long)(long long)v);
+  __syncthreads();
+  return (long long)*s_sum;
+}
+
+// The lane's share of the CU's moments (eq_value's order) into s_V: the sum
+// over its sub-blocks, a wave sum, then one 64-bit LDS add per wave and value
+// (integer: any order).
+template <int NCP, int SB>
+__device__ __forceinline__ void br_accumulate(const int (&S)[SB][5], int u, const int (&v)[SB], long long* s_V) {
+  constexpr int NV = NCP == 3 ? kNumMom : kNumVal2;
+#pragma unroll
+  for (int k = 0; k < NV; k++) {
+    long long t = 0;
+#pragma unroll
+    for (int q = 0; q < SB; q++) t += eq_value<NCP>(k, S[q], u, v[q]);
+    t = br_wave_sum64(t);
+    if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(s_V + k), (unsigned long long)t);
+    __builtin_amdgcn_sched_barrier(0);  // one value at a time, not 24 of them in flight
+  }
+}
+
+__device__ __forceinline__ long long br_rate(float lambda, int bits) {
+  return (long long)(int)floorf(__fmul_rn(lambda, (float)bits));
+}
+
+// NT lanes, SB sub-blocks per lane: sub-block tid + q * NT, q < SB, so a lane's
+// sub-blocks share their column (NT is a multiple of the CU's sub-block row).
+template <int NT, int SB>
+__global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
+  __shared__ uint4 s_coef[48];
+  __shared__ uint2 s_pm[NT * SB * 4];  // P_m, int16 [h][w]: 16 samples per sub-block
+  __shared__ long long s_V[kNumMom];
+  __shared__ double s_M[42];
+  __shared__ unsigned long long s_sum;
+  const int tid = threadIdx.x, i = blockIdx.x;
+  const int ncus = p.ncusDev ? min(max(*p.ncusDev, 0), p.maxCus) : p.maxCus;
+  if (i >= ncus) return;
+  const McBiCu cu = p.cus[i];
+  // vame_affine_mc_bi's validity rules
+  bool ok = br_size_ok(cu.w) && br_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 3) == 0;
+  ok = ok && cu.x <= p.W - cu.w && cu.y <= p.H - cu.h;  // after the size test: no overflow
+  ok = ok && cu.ref0 >= 0 && cu.ref0 < p.nrefs && br_cp_ok(cu.ncps0, cu.c0);
+  ok = ok && cu.ref1 >= -1 && cu.ref1 < p.nrefs;
+  if (cu.ref1 >= 0) ok = ok && br_cp_ok(cu.ncps1, cu.c1);
+  const int nsb = ok ? (cu.w * cu.h) >> 4 : 0;  // an invalid descriptor goes with the smallest class
+  if ((nsb <= 64 ? 64 : nsb <= 256 ? 256 : 1024) != NT * SB) return;
+  if (!ok) {
+    if (tid == 0) {
+      p.out[i] = cu;
+      p.cost[i] = 0;
+      atomicOr(p.bad, 1);
+    }
+    return;
+  }
+  if (tid < 48) s_coef[tid] = reinterpret_cast<const uint4*>(&kCoefTab)[tid];
+  __syncthreads();
+
+  const int W = p.W, H = p.H;
+  const int lw = 31 - __clz(cu.w), lh = 31 - __clz(cu.h);
+  const bool active = tid < nsb;          // the lane holds a sub-block
+  const int nq = SB == 1 ? 1 : nsb / NT;  // and, in a CU that fills the workgroup, nq of them (uniform)
+  const int sx0 = (tid & ((cu.w >> 2) - 1)) << 2, sy0 = (tid >> (lw - 2)) << 2;
+  const int syStep = (NT >> (lw - 2)) << 2;  // rows between a lane's sub-blocks
+  Geo g;
+  g.x = cu.x; g.y = cu.y; g.lw = lw; g.lh = lh; g.w = cu.w; g.h = cu.h;
+  int bA[6], bB[6];  // best CPMVs of hypothesis 0 / 1
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    bA[k] = cu.c0[k];
+    bB[k] = cu.c1[k];
+  }
+  const uint16_t* __restrict__ ref0 =
+      cu.ref0 == 0 ? p.refs[0] : cu.ref0 == 1 ? p.refs[1] : cu.ref0 == 2 ? p.refs[2] : p.refs[3];
+  const uint16_t* __restrict__ ref1 =
+      cu.ref1 == 0 ? p.refs[0] : cu.ref1 == 1 ? p.refs[1] : cu.ref1 == 2 ? p.refs[2] : p.refs[3];
+
+  uint2 O[SB][4] = {};
+  if (active) {
+    // x, sx are multiples of 4 and so is W: every row of a block is 8-byte aligned
+    const char* base = reinterpret_cast<const char*>(p.cur);
+    const size_t bw = (size_t)W * 2u;
+#pragma unroll
+    for (int q = 0; q < SB; q++) {
+      if (q >= nq) break;
+      const size_t b0 = ((size_t)(cu.y + sy0 + q * syStep) * W + cu.x + sx0) * 2u;
+#pragma unroll
+      for (int r = 0; r < 4; r++) O[q][r] = *reinterpret_cast<const uint2*>(base + (b0 + r * bw));
+    }
+  }
+
+  // A uni descriptor (copied through with vame_affine_mc's cost) and rounds = 0
+  // are round 0 cut after its first cost: hypothesis 0 held, and for a bi
+  // descriptor hypothesis 1 predicted as given.  There is one prediction site:
+  // step -1 of a round predicts the fixed hypothesis, steps 0 .. niter the
+  // moving one.
+  const bool uni = cu.ref1 < 0;
+  const int nrounds = (uni || p.rounds == 0) ? 1 : p.rounds;
+  long long bestCost = 0x7fffffffffffffffll;  // round 0's first cost, the descriptor's own, always replaces it
+
+#pragma unroll 1
+  for (int t = 0; t < nrounds; t++) {
+    const bool m1 = (t & 1) == 0;  // round 0 moves hypothesis 1
+    int cf[6], cc[6];              // the fixed hypothesis, the moving one's current CPMVs
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      cf[k] = m1 ? bA[k] : bB[k];
+      cc[k] = m1 ? bB[k] : bA[k];
+    }
+    const int nF = m1 ? cu.ncps0 : cu.ncps1, nM = m1 ? cu.ncps1 : cu.ncps0;
+    const uint16_t* __restrict__ refF = m1 ? ref0 : ref1;
+    const uint16_t* __restrict__ refM = m1 ? ref1 : ref0;
+    const int bitsF = affine_bits(cf, nF) + kRuiBits;
+    const int niter = (uni || p.rounds == 0) ? 0 : nM == 3 ? 4 : 5;
+    int accF[SB][4][4] = {};
+    uint2 Of[SB][4] = {};  // 2 cur - P_fixed, packed int16
+#pragma unroll 1
+    for (int it = -1;; it++) {
+      const bool fix = it < 0;
+      // the lane's geometry is loop-invariant: hidden from the optimizer, or every
+      // address and monomial derived from it is hoisted and held across the loop
+      int sx = sx0, sy = sy0;
+      opaque(sx);
+      opaque(sy);
+      int s = 0;
+      if (active) {
+        int cx[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) cx[k] = fix ? cf[k] : cc[k];
+#pragma unroll
+        for (int q = 0; q < SB; q++) {
+          if (q >= nq) break;
+          const int syq = sy + q * syStep;
+          int acc[4][4];
+          br_hyp_acc(fix ? refF : refM, cu.x, cu.y, lw, lh, cx, fix ? nF : nM, sx, syq, W, H, s_coef, acc);
+          if (fix) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              int d[4];
+#pragma unroll
+              for (int c = 0; c < 4; c++) {
+                accF[q][r][c] = acc[r][c];
+                const unsigned o = c < 2 ? O[q][r].x : O[q][r].y;
+                d[c] = 2 * (int)((c & 1) ? o >> 16 : o & 0xFFFFu) - clampi(acc[r][c] >> 10, 0, 1023);
+              }
+              Of[q][r] = make_uint2(pack16(d[0], d[1]), pack16(d[2], d[3]));
+            }
+          }
+          if (!fix || uni) {  // uni: (2 * acc) >> 11 == acc >> 10, the cost below is vame_affine_mc's
+            uint2 P[4];
+            br_pack_bi(acc, accF[q], P);
+            s += satd_4x4(O[q], P);
+            // P_m for the gradient step (unused after the last cost)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+              s_pm[((syq + r) * cu.w + sx) >> 2] =
+                  make_uint2(pack16(clampi(acc[r][0] >> 10, 0, 1023), clampi(acc[r][1] >> 10, 0, 1023)),
+                             pack16(clampi(acc[r][2] >> 10, 0, 1023), clampi(acc[r][3] >> 10, 0, 1023)));
+          }
+        }
+      }
+      if (fix) {
+        if (!uni) continue;
+        it = 0;
+      }
+      const int bitsM = uni ? 0 : affine_bits(cc, nM) + kRuiBits;
+      const long long cost = br_block_sum<NT>(s, &s_sum) + br_rate(p.lambda, bitsM + bitsF);
+      if (cost < bestCost) {
+        bestCost = cost;
+        if (!uni) {
+#pragma unroll
+          for (int k = 0; k < 6; k++) {
+            if (m1)
+              bB[k] = cc[k];
+            else
+              bA[k] = cc[k];
+          }
+        }
+      }
+      if (it == niter) break;
+
+      // one step of the search's update on P_m with e = 2 cur - P_f - P_m
+      if (tid < kNumMom) s_V[tid] = 0;
+      __syncthreads();
+      int S[SB][5] = {};
+      int vq[SB];
+#pragma unroll
+      for (int q = 0; q < SB; q++) vq[q] = sy + q * syStep + 2;
+      if (active) {
+        const uint16_t* pm16 = reinterpret_cast<const uint16_t*>(s_pm);
+        const int xl = max(sx - 1, 0), xr = min(sx + 4, cu.w - 1);
+#pragma unroll
+        for (int q = 0; q < SB; q++) {
+          if (q >= nq) break;
+          const int syq = sy + q * syStep;
+          uint4 X[6];
+#pragma unroll
+          for (int k = 0; k < 6; k++) {
+            const int row = clampi(syq - 1 + k, 0, cu.h - 1) * cu.w;
+            const uint2 pq = s_pm[(row + sx) >> 2];
+            X[k] = ext_row(pq, (unsigned)pm16[row + xl] << 16, (unsigned)pm16[row + xr]);
+          }
+          grad_sb(sx, syq, g, X, Of[q], S[q]);
+        }
+      }
+      if (nM == 3)
+        br_accumulate<3, SB>(S, sx + 2, vq, s_V);
+      else
+        br_accumulate<2, SB>(S, sx + 2, vq, s_V);
+      __syncthreads();
+      if (tid < 64) {  // the first wave solves; the deltas come back in s_M[0 .. 2 nM)
+        double dd[6];
+        if (nM == 3)
+          seg_solve<3, true>(s_V, s_M, kEqMap.v, tid, 64, true, false, lw, lh, dd);
+        else
+          seg_solve<2, true>(s_V, s_M, kEqMap.v, tid, 64, true, false, lw, lh, dd);
+      }
+      __syncthreads();
+      bool moved = false;
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        if (j < 2 * nM) {  // a 2-CP hypothesis never changes LB
+          const double d = s_M[j == 1 ? 2 : j == 2 ? 1 : j];  // LT = (d0, d2), RT = (d1, d3), LB = (d4, d5)
+          int v = (int)((unsigned)cc[j] + (unsigned)scale_delta(d));
+          v = clampi(v, kMvMin, kMvMax);
+          const int pos = (j & 1) ? cu.y : cu.x, lim = (j & 1) ? H : W;
+          v = clampi(v, shl(-128 - 8 - pos + 1, 4), shl(lim + 8 - pos - 1, 4));  // clipMv
+          moved = moved || v != cc[j];
+          cc[j] = v;
+        }
+      }
+      __syncthreads();  // s_M, s_V and s_pm are free again
+      // unchanged CPMVs repeat this iteration's prediction and cost: never strictly better
+      if (!moved) break;
+    }
+  }
+  if (tid == 0) {
+    McBiCu o = cu;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      o.c0[k] = bA[k];
+      o.c1[k] = bB[k];
+    }
+    p.out[i] = o;
+    p.cost[i] = bestCost;
+  }
+}
+
+hipError_t birefine_launch(const BiRefineParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL((birefine_kernel<64, 1>), dim3(p.maxCus), dim3(64), 0, stream, p);
+  hipLaunchKernelGGL((birefine_kernel<256, 1>), dim3(p.maxCus), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((birefine_kernel<512, 2>), dim3(p.maxCus), dim3(512), 0, stream, p);
+  return hipGetLastError();
+}
+
+}  // namespace vame

@@ -16,6 +16,7 @@
 #include "../../include/vame.h"
 #include "vame_kernel.h"
 #include "vame_bipred.h"
+#include "vame_birefine.h"
 
 #if VAME_SPLIT_TU
 namespace vame {
@@ -1245,6 +1246,40 @@ int vame_partition_bi(vame_ctx* c, const vame_poc_result* res, int nrefs, int pr
   p.nCtus = c->nCtus;
   p.ctusPerRow = c->ctusPerRow;
   VAME_HIP(partition_launch(p, (hipStream_t)stream, true));
+  return VAME_OK;
+}
+
+int vame_bipred_refine(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda, int rounds,
+                       vame_mc_bicu* out, int64_t* cost, int32_t* bad, void* stream) {
+  if (!c || !cur || !refs || !cus || !out || !cost || !bad) return VAME_E_INVALID;
+  if (nrefs < 1 || nrefs > 4 || rounds < 0 || rounds > 4 || max_cus < 0 || max_cus > VAME_MC_MAX_CUS)
+    return VAME_E_INVALID;
+  // the kernel reads window rows as dwords and block rows as 8-byte words
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  BiRefineParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nrefs; r++) {
+    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
+    p.refs[r] = refs[r];
+  }
+  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
+  if (max_cus == 0) return VAME_OK;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cus = reinterpret_cast<const McBiCu*>(cus);
+  p.out = reinterpret_cast<McBiCu*>(out);
+  p.cost = cost;
+  p.bad = bad;
+  p.maxCus = max_cus;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.rounds = rounds;
+  p.lambda = lambda;
+  p.ncusDev = ncus_dev;
+  VAME_HIP(birefine_launch(p, (hipStream_t)stream));
   return VAME_OK;
 }
 

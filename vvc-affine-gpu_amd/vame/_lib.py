@@ -21,7 +21,7 @@ EXPORTS = (
     "vame_log_writer_sizes", "vame_log_writer_flush_at", "vame_template_coverage", "vame_pack_records",
     "vame_count_lines_ranges", "vame_set_max_pairs", "vame_get_max_pairs", "vame_affine_mc",
     "vame_affine_mc_dev", "vame_partition", "vame_partition_table", "vame_affine_mc_bi", "vame_bipred",
-    "vame_partition_bi",
+    "vame_partition_bi", "vame_bipred_refine",
 )
 
 
@@ -64,6 +64,7 @@ def lib():
         L.vame_bipred.argtypes = [P, P, P, I, F, ctypes.POINTER(PocResult), I, P, P, P]
         L.vame_partition_bi.argtypes = [P, ctypes.POINTER(PocResult), I, I, ctypes.c_int64, P, P, ctypes.c_int64,
                                         P, P, P, P, P, P, P, P]
+        L.vame_bipred_refine.argtypes = [P, P, P, I, P, I, P, F, I, P, P, P, P]
         L.vame_num_ctus.argtypes = [I, I]
         L.vame_cus_per_ctu.argtypes = [I]
         L.vame_num_groups.argtypes = [I]

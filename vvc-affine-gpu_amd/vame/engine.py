@@ -441,6 +441,96 @@ class Engine:
                                       int(bi_penalty), *(V(out[k].data_ptr()) for k in B.KEYS), self._stream()))
         return out
 
+    # ---- refinement of bi-predicted CUs
+    def bipred_refine(self, cus: torch.Tensor, refs, cur, lam: float, rounds: int = 2,
+                      count: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                      cost: torch.Tensor | None = None):
+        """vame_bipred_refine: for every bi descriptor of cus (int32 [n, 20],
+        vame.bipred.BICU_FIELDS) hold one hypothesis, re-estimate the other
+        against what the held one leaves to explain, and swap, `rounds` times
+        (0..4; round 0 moves the second hypothesis).  Returns (out, cost, bad):
+        the descriptors with their refined CPMVs, int64 [n] their bi costs --
+        exactly affine_mc_bi's costs of `out`, never above those of `cus` --
+        and the int32 flag of an invalid descriptor (copied through, cost 0).
+        Uni descriptors (ref1 = -1) pass through with their uni cost.  count:
+        an int32 scalar on the device, the number of descriptors to work on
+        (entries past it stay untouched); out may be cus.  Reads nothing on the
+        host; asynchronous on the current stream.  Not available under PROF."""
+        def bad_cus(t):
+            return (t.dim() != 2 or t.shape[1] != 20 or t.dtype != torch.int32 or t.device != self.device
+                    or not t.is_contiguous())
+        if bad_cus(cus):
+            raise ValueError(f"cus must be a contiguous int32 [n, 20] tensor on {self.device}")
+        if not 0 <= int(rounds) <= 4:
+            raise ValueError("rounds must be in 0..4")
+        refs = [self._frame(r) for r in refs]
+        if not 1 <= len(refs) <= 4:
+            raise ValueError("bipred_refine takes 1..4 reference frames")
+        cur = self._frame(cur)
+        n = cus.shape[0]
+        if count is not None and (count.numel() != 1 or count.dtype != torch.int32 or count.device != self.device):
+            raise ValueError(f"count must be an int32 scalar on {self.device}")
+        if out is None:
+            out = torch.empty_like(cus)
+        elif bad_cus(out) or out.shape[0] != n:
+            raise ValueError(f"out must be a contiguous int32 [{n}, 20] tensor on {self.device}")
+        if cost is None:
+            cost = torch.empty(n, dtype=torch.int64, device=self.device)
+        elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
+              or not cost.is_contiguous()):
+            raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+        check(lib().vame_bipred_refine(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(count),
+                                       float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
+        return out, cost, bad
+
+    def refine_partition(self, part: dict, refs, cur, lam: float, rounds: int = 2) -> dict:
+        """bipred_refine on the leaves of a partition_bi() result, their count
+        read on the device.  Returns a new dict for predict_partition: the
+        entries of `part` with `cus` replaced by the refined descriptors, plus
+        leaf_cost int64 [nCtus*64] (the first ncus entries written) and bad.
+        `part` is not modified; no host read."""
+        if part["cus"].dim() != 2 or part["cus"].shape[1] != 20:
+            raise ValueError("refine_partition needs a partition_bi() result")
+        cus, cost, bad = self.bipred_refine(part["cus"], refs, cur, lam, rounds, count=part["ncus"])
+        out = dict(part)
+        out["cus"], out["leaf_cost"], out["bad"] = cus, cost, bad
+        return out
+
+    def refine_bipred(self, cur, refs, lam: float, result: dict, bi: dict, rounds: int = 2,
+                      preds: int | None = None) -> dict:
+        """bipred_refine on every candidate CU with a pair (bi_sel >= 0) of a
+        bipred() result `bi` over `result`.  Returns a new bi dict: cost with
+        the refined costs scattered back, sel unchanged, and per alignment the
+        refined descriptors `cus` and their `rows` (None for an alignment
+        outside `preds`).  partition_bi() takes it as its bi argument; the bi
+        leaves it emits still carry the search's CPMVs, and refine_partition()
+        with the same `rounds` turns them into the descriptors refined here, at
+        the costs the partition used.  `bi` is not modified.  Reads the
+        selection on the host (synchronizes)."""
+        from . import bipred as B
+        from . import partition as P
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds:
+            raise ValueError("preds must hold a PRED and only bits 0..3")
+        self._check_result(result, preds, "refine_bipred")
+        self._check_bi(bi, preds)
+        out = {"cost": [None, None], "sel": [None, None], "cus": [None, None], "rows": [None, None]}
+        for a in (0, 1):
+            if not (preds >> (2 * a)) & 3:
+                continue
+            sel = bi["sel"][a]
+            rows = torch.nonzero(sel >= 0).reshape(-1)
+            res_a = {k: v for k, v in result.items() if (preds >> MODES.index(k[1])) & 1}
+            cus = B.bicus_from_sel(self.W, self.H, a, res_a, sel, rows)
+            cost = bi["cost"][a].clone()
+            if rows.numel():
+                cus, c, _ = self.bipred_refine(cus, refs, cur, lam, rounds)
+                cost[rows] = c
+            out["cost"][a], out["sel"][a], out["cus"][a], out["rows"][a] = cost, sel, cus, rows.to(torch.int32)
+        return out
+
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to
         code one alignment only.  Returns {(refIdx, MODE): (cost, cpmv)}."""

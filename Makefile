@@ -31,23 +31,28 @@ KFLAGS     := -mllvm -simplifycfg-sink-common=false -mllvm -structurizecfg-skip-
 KFLAGS_2CP := -mllvm -simplifycfg-sink-common=false -mllvm -simplifycfg-hoist-common=false \
               -mllvm -structurizecfg-skip-uniform-regions=true
 
-LIB_SRCS := $(CSRC)/vame_engine.hip $(CSRC)/vame_kernels_2cp.hip $(CSRC)/vame_mc.hip $(CSRC)/vame_partition.hip $(CSRC)/vame_bipred.hip $(CSRC)/vame_birefine.hip $(CSRC)/vame_hostlogic.cpp $(CSRC)/vame_io.cpp
-LIB_HDRS := $(CSRC)/vame_kernel.h $(CSRC)/vame_bipred.h $(CSRC)/vame_birefine.h $(CSRC)/vame_tables.h include/vame.h
+# The library's units, one word each: <object tag>=<source>[=<variable with its
+# own flags>].  Everything below -- build_lib, resource-usage, the
+# dependencies -- goes over this list: a new unit is one word here.
+UNITS := engine=vame_engine.hip=KFLAGS 2cp=vame_kernels_2cp.hip=KFLAGS_2CP mc=vame_mc.hip \
+         partition=vame_partition.hip bipred=vame_bipred.hip birefine=vame_birefine.hip \
+         hostlogic=vame_hostlogic.cpp io=vame_io.cpp
+unit_tag   = $(word 1,$(subst =, ,$(1)))
+unit_src   = $(CSRC)/$(word 2,$(subst =, ,$(1)))
+unit_flags = $($(word 3,$(subst =, ,$(1))))
+define NL
+
+
+endef
+
+LIB_SRCS := $(foreach u,$(UNITS),$(call unit_src,$(u)))
+LIB_HDRS := $(wildcard $(CSRC)/*.h) include/vame.h
 OBJDIR   := $(PKG)/build
 # $(call build_lib,<output .so>,<extra flags>): every unit with its own flags, then one link
 define build_lib
 	@mkdir -p $(LIBDIR) $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).engine.o $(CSRC)/vame_engine.hip
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS_2CP) $(2) -c -o $(OBJDIR)/$(notdir $(1)).2cp.o $(CSRC)/vame_kernels_2cp.hip
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).mc.o $(CSRC)/vame_mc.hip
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).partition.o $(CSRC)/vame_partition.hip
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).bipred.o $(CSRC)/vame_bipred.hip
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).birefine.o $(CSRC)/vame_birefine.hip
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).hostlogic.o $(CSRC)/vame_hostlogic.cpp
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $(OBJDIR)/$(notdir $(1)).io.o $(CSRC)/vame_io.cpp
-	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $(1) $(OBJDIR)/$(notdir $(1)).engine.o \
-	    $(OBJDIR)/$(notdir $(1)).2cp.o $(OBJDIR)/$(notdir $(1)).mc.o $(OBJDIR)/$(notdir $(1)).partition.o \
-	    $(OBJDIR)/$(notdir $(1)).bipred.o $(OBJDIR)/$(notdir $(1)).birefine.o $(OBJDIR)/$(notdir $(1)).hostlogic.o $(OBJDIR)/$(notdir $(1)).io.o
+	$(foreach u,$(UNITS),$(HIPCC) $(HIPFLAGS) $(call unit_flags,$(u)) $(2) -c -o $(OBJDIR)/$(notdir $(1)).$(call unit_tag,$(u)).o $(call unit_src,$(u))$(NL))
+	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $(1) $(foreach u,$(UNITS),$(OBJDIR)/$(notdir $(1)).$(call unit_tag,$(u)).o)
 endef
 
 all: lib cli synth oracle probe
@@ -95,12 +100,7 @@ oracle:
 	@if [ -d /root/reference ]; then $(MAKE) -s -C oracle ref; fi
 
 resource-usage:
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_engine.hip
-	$(HIPCC) $(HIPFLAGS) $(KFLAGS_2CP) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_kernels_2cp.hip
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_mc.hip
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_partition.hip
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_bipred.hip
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(CSRC)/vame_birefine.hip
+	$(foreach u,$(UNITS),$(if $(filter %.hip,$(call unit_src,$(u))),$(HIPCC) $(HIPFLAGS) $(call unit_flags,$(u)) -Rpass-analysis=kernel-resource-usage -c -o /dev/null $(call unit_src,$(u))$(NL)))
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(OBJDIR)

@@ -1,36 +1,10 @@
 // vame_bipred.h -- affine bi-prediction (vame_affine_mc_bi, vame_bipred;
-// include/vame.h): the parameter blocks and launch functions of
-// vame_bipred.hip.
+// include/vame.h): vame_bipred's parameter block and launch
+// function (vame_affine_mc_bi's are vame_mc_core.h's McBiParams, mc_bi_launch).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "vame_mc_core.h"
 
 namespace vame {
-
-// device view of vame_mc_bicu (include/vame.h): 20 int32; the first 12 are a McCu
-struct McBiCu {
-  int32_t x, y, w, h, ref0;
-  int32_t ncps0, c0[6];  // LTx, LTy, RTx, RTy, LBx, LBy
-  int32_t ref1;          // -1: uni-predicted from (ref0, c0)
-  int32_t ncps1, c1[6];
-};
-
-struct McBiParams {
-  const uint16_t* cur;  // NULL when cost is
-  const uint16_t* refs[4];
-  const McBiCu* cus;
-  uint16_t* pred;    // or NULL
-  int64_t* cost;     // or NULL
-  int32_t* bad;
-  int32_t* offs;     // [ncus + 1]: first sub-block of each descriptor; the total
-  int32_t* blockSum; // [1024]: sub-blocks per scan block
-  int ncus, nrefs, W, H;
-  float lambda;
-  const int32_t* ncusDev;  // or NULL: the count is ncus
-};
-// The three launches of one vame_affine_mc_bi call on `stream` (ncus >= 1).
-hipError_t mc_bi_launch(const McBiParams& p, hipStream_t stream);
 
 // A candidate CU of the frame's fixed geometry that lies wholly in the frame
 // (vame_create builds the table: the aligned candidates first, CTUs ascending,

@@ -1,16 +1,13 @@
 // vame_bipred.hip -- affine bi-prediction (include/vame.h).
 //
-// A hypothesis is one prediction of vame_affine_mc (vame_mc.hip): sub-block MV
-// and spread test, roundMv / clipMv against the CU position, clamp-to-edge
-// window, the 6-tap two-stage filter -- up to its second-stage accumulator
-// acc = sum + 512 + (8192 << 6), whose uni sample is clampi(acc >> 10, 0, 1023).
-// The bi sample of two hypotheses is clampi((acc0 + acc1) >> 11, 0, 1023): the
-// sum of the unrounded second-stage values, rounded once.
+// A hypothesis is one prediction of vame_affine_mc up to its second-stage
+// accumulator (mc_hyp_acc, vame_mc_core.h); the bi sample of two hypotheses is
+// the sum of their accumulators, rounded once (mc_bi_pack).
 //
-//   vame_affine_mc_bi   mc_bi_count_kernel / mc_bi_offsets_kernel /
-//                       mc_bi_predict_kernel: vame_affine_mc's three launches
-//                       on 20-word descriptors, one lane per 4x4 sub-block, two
-//                       filter passes into two accumulator sets
+//   vame_affine_mc_bi   mc_count_kernel / mc_offsets_kernel (vame_mc_core.h)
+//                       on 20-word descriptors, then mc_bi_predict_kernel:
+//                       vame_affine_mc's three launches, one lane per 4x4
+//                       sub-block, two filter passes into two accumulator sets
 //   vame_bipred         the best reference pair of every in-frame candidate CU.
 //                       The candidates are fixed geometry: vame_create builds
 //                       their table and the map group of 16 sub-blocks ->
@@ -30,143 +27,22 @@
 #include <algorithm>
 
 #include "vame_bipred.h"
-#include "vame_kernel.h"
 
 namespace vame {
 
-constexpr int kBiScanBlock = 1024;  // descriptors per scan block (one per thread)
-constexpr int kBiThreads = 256;     // prediction workgroups
-constexpr int kBiMaxBlocks = 2048;  // vame_affine_mc_bi's prediction grid (grid-strided beyond it)
+constexpr int kBiThreads = 256;  // vame_bipred's workgroups
 constexpr long long kBiInf = 0x7fffffffffffffffll;
-static_assert(kMcMaxCus <= kBiScanBlock * kBiScanBlock, "two scan levels");
-static_assert(sizeof(McBiCu) == 80, "vame_mc_bicu layout");
 static_assert(sizeof(BiCand) == 16, "one 16-byte load");
 
-// Sum over the workgroup's 1024 threads: the exclusive prefix of `v` in thread
-// order (return value) and the total (every thread).
-__device__ __forceinline__ int bi_block_scan_1024(int v, int* s_wave, int& total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kBiScanBlock / 64; w++) {
-    const int s = s_wave[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  total = all;
-  return before + incl - v;
-}
-
-__device__ __forceinline__ bool bi_size_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
-__device__ __forceinline__ bool bi_mv_ok(int v) { return v >= kMvMin && v <= kMvMax; }
-__device__ __forceinline__ bool bi_cp_ok(int ncps, const int32_t (&c)[6]) {
-  bool ok = (ncps == 2 || ncps == 3) && bi_mv_ok(c[0]) && bi_mv_ok(c[1]) && bi_mv_ok(c[2]) && bi_mv_ok(c[3]);
-  if (ncps == 3) ok = ok && bi_mv_ok(c[4]) && bi_mv_ok(c[5]);
-  return ok;
-}
-
-__device__ __forceinline__ int mc_bi_ncus(const McBiParams& p) {
-  return p.ncusDev ? min(max(*p.ncusDev, 0), p.ncus) : p.ncus;
-}
-
-__global__ __launch_bounds__(kBiScanBlock) void mc_bi_count_kernel(McBiParams p) {
-  __shared__ int s_wave[kBiScanBlock / 64];
-  const int i = blockIdx.x * kBiScanBlock + threadIdx.x;
-  const int ncus = mc_bi_ncus(p);
-  int n = 0;
-  bool flag = false;
-  if (i < ncus) {
-    const McBiCu cu = p.cus[i];
-    bool ok = bi_size_ok(cu.w) && bi_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 3) == 0;
-    ok = ok && cu.x <= p.W - cu.w && cu.y <= p.H - cu.h;  // after the size test: no overflow
-    ok = ok && cu.ref0 >= 0 && cu.ref0 < p.nrefs && bi_cp_ok(cu.ncps0, cu.c0);
-    ok = ok && cu.ref1 >= -1 && cu.ref1 < p.nrefs;
-    if (cu.ref1 >= 0) ok = ok && bi_cp_ok(cu.ncps1, cu.c1);
-    n = ok ? (cu.w * cu.h) >> 4 : 0;
-    flag = !ok;
-    if (p.cost) p.cost[i] = 0;
-  }
-  const unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
-  if (m && (int)__lane_id() == __builtin_ctzll(m)) atomicOr(p.bad, 1);
-  int total;
-  const int excl = bi_block_scan_1024(n, s_wave, total);
-  if (i < ncus) p.offs[i] = excl;
-  if (threadIdx.x == 0) p.blockSum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBiScanBlock) void mc_bi_offsets_kernel(McBiParams p) {
-  __shared__ int s_wave[kBiScanBlock / 64];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int ncus = mc_bi_ncus(p);
-  int base;
-  bi_block_scan_1024(tid < b ? p.blockSum[tid] : 0, s_wave, base);
-  const int i = b * kBiScanBlock + tid;
-  if (i < ncus) p.offs[i] += base;
-  // scan blocks past a device-side count hold no sub-blocks
-  if (b == (int)gridDim.x - 1 && tid == 0) p.offs[ncus] = base + p.blockSum[b];
-}
-
-// Sum over the 16 lanes of a DPP row, in every lane of the row.
-__device__ __forceinline__ int bi_row_sum16(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);   // quad_perm:[1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);   // quad_perm:[2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);  // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);  // row_mirror
-  return v;
-}
-
-// The second-stage accumulators of one hypothesis for the sub-block at (sx, sy)
-// of the CU (x, y, 2^lw, 2^lh): mc_predict_kernel's steps up to the rounding
-// shift.  Every load is clamped to the frame, whatever the CPMVs hold.
-__device__ __forceinline__ void hyp_acc(const uint16_t* __restrict__ ref, int x, int y, int lw, int lh,
-                                        const int (&cp)[6], int ncps, int sx, int sy, int W, int H,
-                                        const uint4* s_coef, int (&acc)[4][4]) {
-  const MvField f = mv_field(cp, ncps, lw, lh);
-  const int px = f.spread ? (1 << (lw - 1)) : sx + 2, py = f.spread ? (1 << (lh - 1)) : sy + 2;
-  int mx = f.bx + __mul24(f.hx, px) + __mul24(f.vx, py);
-  int my = f.by + __mul24(f.hy, px) + __mul24(f.vy, py);
-  mx = (mx + 64 - (mx >= 0)) >> 7;  // roundMv (aux_functions.cl:38-47)
-  my = (my + 64 - (my >= 0)) >> 7;
-  // clipMv (aux_functions.cl:51-67) on the frame position of the MV's target
-  const int ax = clampi(mx + shl(x, 4), -135 * 16, (W + 7) * 16);
-  const int ay = clampi(my + shl(y, 4), -135 * 16, (H + 7) * 16);
-  const int fx = ax & 15, fy = ay & 15;
-  const int wx = (ax >> 4) + sx - 2, wy = (ay >> 4) + sy - 2;  // window origin (frame)
-  const uint4 KA = s_coef[fx * 3], KB = s_coef[fx * 3 + 1];
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 4; c++) acc[r][c] = 524800;  // (1 << 9) + (8192 << 6)
-  filter_rows_global(ref, wx, wy, W, H, KA, KB, reinterpret_cast<const unsigned*>(s_coef), fy, acc);
-}
-
-__device__ __forceinline__ void bi_pack(const int (&a)[4][4], const int (&b)[4][4], uint2 (&P)[4]) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    int s[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) s[c] = clampi((a[r][c] + b[r][c]) >> 11, 0, 1023);
-    P[r] = make_uint2(pack16(s[0], s[1]), pack16(s[2], s[3]));
-  }
-}
-
-__global__ __launch_bounds__(kBiThreads) void mc_bi_predict_kernel(McBiParams p) {
+__global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McBiParams p) {
   __shared__ uint4 s_coef[48];
   const int tid = threadIdx.x;
   if (tid < 48) s_coef[tid] = reinterpret_cast<const uint4*>(&kCoefTab)[tid];
   __syncthreads();
   const int W = p.W, H = p.H;
-  const int ncus = mc_bi_ncus(p);
+  const int ncus = mc_ncus(p.ncusDev, p.ncus);
   const int total = p.offs[ncus];
-  for (int g = blockIdx.x * kBiThreads + tid; g < total; g += (int)gridDim.x * kBiThreads) {
+  for (int g = blockIdx.x * kMcThreads + tid; g < total; g += (int)gridDim.x * kMcThreads) {
     // the last descriptor whose offset is <= g (descriptors without
     // sub-blocks share their successor's offset and are never found)
     int lo = 0, hi = ncus;
@@ -186,18 +62,18 @@ __global__ __launch_bounds__(kBiThreads) void mc_bi_predict_kernel(McBiParams p)
     const uint16_t* __restrict__ ref0 =
         cu.ref0 == 0 ? p.refs[0] : cu.ref0 == 1 ? p.refs[1] : cu.ref0 == 2 ? p.refs[2] : p.refs[3];
     int acc[4][4];
-    hyp_acc(ref0, cu.x, cu.y, lw, lh, cp0, cu.ncps0, sx, sy, W, H, s_coef, acc);
+    mc_hyp_acc(ref0, cu.x, cu.y, lw, lh, cp0, cu.ncps0, sx, sy, W, H, s_coef, acc);
     uint2 P[4];
     int bits = affine_bits(cp0, cu.ncps0) + kRuiBits;
     if (cu.ref1 >= 0) {
       const uint16_t* __restrict__ ref1 =
           cu.ref1 == 0 ? p.refs[0] : cu.ref1 == 1 ? p.refs[1] : cu.ref1 == 2 ? p.refs[2] : p.refs[3];
       int acc1[4][4];
-      hyp_acc(ref1, cu.x, cu.y, lw, lh, cp1, cu.ncps1, sx, sy, W, H, s_coef, acc1);
-      bi_pack(acc, acc1, P);
+      mc_hyp_acc(ref1, cu.x, cu.y, lw, lh, cp1, cu.ncps1, sx, sy, W, H, s_coef, acc1);
+      mc_bi_pack(acc, acc1, P);
       bits += affine_bits(cp1, cu.ncps1) + kRuiBits;
     } else {
-      bi_pack(acc, acc, P);  // (2 * acc) >> 11 == acc >> 10
+      mc_bi_pack(acc, acc, P);  // (2 * acc) >> 11 == acc >> 10
     }
 
     // x, sx are multiples of 4 and so is W: every row of the block is 8-byte aligned
@@ -212,22 +88,16 @@ __global__ __launch_bounds__(kBiThreads) void mc_bi_predict_kernel(McBiParams p)
       uint2 O[4];
 #pragma unroll
       for (int r = 0; r < 4; r++) O[r] = *reinterpret_cast<const uint2*>(base + (b0 + r * bw));
-      long long v = bi_row_sum16(satd_4x4(O, P));
+      long long v = row_sum16(satd_4x4(O, P));
       // the CU's first lane adds the rate: each hypothesis with its own ruiBits
-      if (local == 0) v += (long long)(int)floorf(__fmul_rn(p.lambda, (float)bits));
+      if (local == 0) v += mc_rate(p.lambda, bits);
       if ((local & 15) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(p.cost + lo), (unsigned long long)v);
     }
   }
 }
 
 hipError_t mc_bi_launch(const McBiParams& p, hipStream_t stream) {
-  const int nb = (p.ncus + kBiScanBlock - 1) / kBiScanBlock;
-  hipLaunchKernelGGL(mc_bi_count_kernel, dim3(nb), dim3(kBiScanBlock), 0, stream, p);
-  hipLaunchKernelGGL(mc_bi_offsets_kernel, dim3(nb), dim3(kBiScanBlock), 0, stream, p);
-  // at most 1024 sub-blocks per descriptor: 4 workgroups
-  const int grid = (int)std::min<long long>(4ll * p.ncus, kBiMaxBlocks);
-  hipLaunchKernelGGL(mc_bi_predict_kernel, dim3(grid), dim3(kBiThreads), 0, stream, p);
-  return hipGetLastError();
+  return mc_launch_concat(p, mc_bi_predict_kernel, stream);
 }
 
 // ------------------------------------------------------------------ vame_bipred
@@ -269,15 +139,15 @@ __device__ __forceinline__ void bi_hyp(const BiRowsParams& p, const BiCand& cd, 
   const int m = bi_model<R>(p, align, cd.row);
   int cp[6];
   bi_load_cp<R>(p, align, m, cd.row, cp);
-  hyp_acc(p.refs[R], cd.xy & 0xFFFF, cd.xy >> 16, cd.shape & 15, (cd.shape >> 4) & 15, cp, 2 + m, sx, sy, p.W, p.H,
-          s_coef, acc);
+  mc_hyp_acc(p.refs[R], cd.xy & 0xFFFF, cd.xy >> 16, cd.shape & 15, (cd.shape >> 4) & 15, cp, 2 + m, sx, sy, p.W,
+             p.H, s_coef, acc);
 }
 
 __device__ __forceinline__ void bi_pair(const BiRowsParams& p, const int (&a)[4][4], const int (&b)[4][4],
                                         const uint2 (&O)[4], bool first, int cand, int pair) {
   uint2 P[4];
-  bi_pack(a, b, P);
-  const int v = bi_row_sum16(satd_4x4(O, P));
+  mc_bi_pack(a, b, P);
+  const int v = row_sum16(satd_4x4(O, P));
   if (first)
     atomicAdd(reinterpret_cast<unsigned long long*>(p.pairSatd + (size_t)cand * kBiPairs + pair),
               (unsigned long long)(long long)v);
@@ -352,8 +222,7 @@ __global__ __launch_bounds__(kBiThreads) void bipred_close_kernel(BiRowsParams p
 #pragma unroll
     for (int r1 = r0 + 1; r1 < 4; r1++, pair++) {
       if (r1 >= p.nrefs) continue;
-      const long long v = p.pairSatd[(size_t)cand * kBiPairs + pair] +
-                          (long long)(int)floorf(__fmul_rn(p.lambda, (float)(bits[r0] + bits[r1])));
+      const long long v = p.pairSatd[(size_t)cand * kBiPairs + pair] + mc_rate(p.lambda, bits[r0] + bits[r1]);
       if (v < best) {
         best = v;
         sel = r0 + 4 * m[r0] + 8 * r1 + 32 * m[r1];

@@ -2,11 +2,7 @@
 // include/vame.h): the parameter block and the launch function
 // of vame_birefine.hip.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "vame_bipred.h"
+#include "vame_mc_core.h"
 
 namespace vame {
 

@@ -23,56 +23,10 @@
 #include <hip/hip_runtime.h>
 
 #include "vame_birefine.h"
-#include "vame_kernel.h"
 
 namespace vame {
 
-static_assert(sizeof(McBiCu) == 80, "vame_mc_bicu layout");
 static_assert(kNumVal2 <= kNumMom, "one moment table for both models");
-
-__device__ __forceinline__ bool br_size_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
-__device__ __forceinline__ bool br_mv_ok(int v) { return v >= kMvMin && v <= kMvMax; }
-__device__ __forceinline__ bool br_cp_ok(int ncps, const int32_t (&c)[6]) {
-  bool ok = (ncps == 2 || ncps == 3) && br_mv_ok(c[0]) && br_mv_ok(c[1]) && br_mv_ok(c[2]) && br_mv_ok(c[3]);
-  if (ncps == 3) ok = ok && br_mv_ok(c[4]) && br_mv_ok(c[5]);
-  return ok;
-}
-
-// The second-stage accumulators of one hypothesis for the sub-block at (sx, sy)
-// of the CU (x, y, 2^lw, 2^lh): vame_affine_mc's prediction up to the rounding
-// shift.  Every load is clamped to the frame, whatever the CPMVs hold.
-__device__ __forceinline__ void br_hyp_acc(const uint16_t* __restrict__ ref, int x, int y, int lw, int lh,
-                                           const int (&cp)[6], int ncps, int sx, int sy, int W, int H,
-                                           const uint4* s_coef, int (&acc)[4][4]) {
-  const MvField f = mv_field(cp, ncps, lw, lh);
-  const int px = f.spread ? (1 << (lw - 1)) : sx + 2, py = f.spread ? (1 << (lh - 1)) : sy + 2;
-  int mx = f.bx + __mul24(f.hx, px) + __mul24(f.vx, py);
-  int my = f.by + __mul24(f.hy, px) + __mul24(f.vy, py);
-  mx = (mx + 64 - (mx >= 0)) >> 7;  // roundMv (aux_functions.cl:38-47)
-  my = (my + 64 - (my >= 0)) >> 7;
-  // clipMv (aux_functions.cl:51-67) on the frame position of the MV's target
-  const int ax = clampi(mx + shl(x, 4), -135 * 16, (W + 7) * 16);
-  const int ay = clampi(my + shl(y, 4), -135 * 16, (H + 7) * 16);
-  const int fx = ax & 15, fy = ay & 15;
-  const int wx = (ax >> 4) + sx - 2, wy = (ay >> 4) + sy - 2;  // window origin (frame)
-  const uint4 KA = s_coef[fx * 3], KB = s_coef[fx * 3 + 1];
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 4; c++) acc[r][c] = 524800;  // (1 << 9) + (8192 << 6)
-  filter_rows_global(ref, wx, wy, W, H, KA, KB, reinterpret_cast<const unsigned*>(s_coef), fy, acc);
-}
-
-// bi samples clampi((a + b) >> 11, 0, 1023), packed rows
-__device__ __forceinline__ void br_pack_bi(const int (&a)[4][4], const int (&b)[4][4], uint2 (&P)[4]) {
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    int s[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) s[c] = clampi((a[r][c] + b[r][c]) >> 11, 0, 1023);
-    P[r] = make_uint2(pack16(s[0], s[1]), pack16(s[2], s[3]));
-  }
-}
 
 __device__ __forceinline__ int br_wave_sum(int v) {
 #pragma unroll
@@ -115,10 +69,6 @@ __device__ __forceinline__ void br_accumulate(const int (&S)[SB][5], int u, cons
   }
 }
 
-__device__ __forceinline__ long long br_rate(float lambda, int bits) {
-  return (long long)(int)floorf(__fmul_rn(lambda, (float)bits));
-}
-
 // NT lanes, SB sub-blocks per lane: sub-block tid + q * NT, q < SB, so a lane's
 // sub-blocks share their column (NT is a multiple of the CU's sub-block row).
 template <int NT, int SB>
@@ -129,15 +79,14 @@ __global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
   __shared__ double s_M[42];
   __shared__ unsigned long long s_sum;
   const int tid = threadIdx.x, i = blockIdx.x;
-  const int ncus = p.ncusDev ? min(max(*p.ncusDev, 0), p.maxCus) : p.maxCus;
-  if (i >= ncus) return;
+  if (i >= mc_ncus(p.ncusDev, p.maxCus)) return;
   const McBiCu cu = p.cus[i];
   // vame_affine_mc_bi's validity rules
-  bool ok = br_size_ok(cu.w) && br_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 3) == 0;
+  bool ok = mc_size_ok(cu.w) && mc_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 3) == 0;
   ok = ok && cu.x <= p.W - cu.w && cu.y <= p.H - cu.h;  // after the size test: no overflow
-  ok = ok && cu.ref0 >= 0 && cu.ref0 < p.nrefs && br_cp_ok(cu.ncps0, cu.c0);
+  ok = ok && cu.ref0 >= 0 && cu.ref0 < p.nrefs && mc_cp_ok(cu.ncps0, cu.c0);
   ok = ok && cu.ref1 >= -1 && cu.ref1 < p.nrefs;
-  if (cu.ref1 >= 0) ok = ok && br_cp_ok(cu.ncps1, cu.c1);
+  if (cu.ref1 >= 0) ok = ok && mc_cp_ok(cu.ncps1, cu.c1);
   const int nsb = ok ? (cu.w * cu.h) >> 4 : 0;  // an invalid descriptor goes with the smallest class
   if ((nsb <= 64 ? 64 : nsb <= 256 ? 256 : 1024) != NT * SB) return;
   if (!ok) {
@@ -227,7 +176,7 @@ __global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
           if (q >= nq) break;
           const int syq = sy + q * syStep;
           int acc[4][4];
-          br_hyp_acc(fix ? refF : refM, cu.x, cu.y, lw, lh, cx, fix ? nF : nM, sx, syq, W, H, s_coef, acc);
+          mc_hyp_acc(fix ? refF : refM, cu.x, cu.y, lw, lh, cx, fix ? nF : nM, sx, syq, W, H, s_coef, acc);
           if (fix) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
@@ -243,7 +192,7 @@ __global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
           }
           if (!fix || uni) {  // uni: (2 * acc) >> 11 == acc >> 10, the cost below is vame_affine_mc's
             uint2 P[4];
-            br_pack_bi(acc, accF[q], P);
+            mc_bi_pack(acc, accF[q], P);
             s += satd_4x4(O[q], P);
             // P_m for the gradient step (unused after the last cost)
 #pragma unroll
@@ -259,7 +208,7 @@ __global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
         it = 0;
       }
       const int bitsM = uni ? 0 : affine_bits(cc, nM) + kRuiBits;
-      const long long cost = br_block_sum<NT>(s, &s_sum) + br_rate(p.lambda, bitsM + bitsF);
+      const long long cost = br_block_sum<NT>(s, &s_sum) + mc_rate(p.lambda, bitsM + bitsF);
       if (cost < bestCost) {
         bestCost = cost;
         if (!uni) {

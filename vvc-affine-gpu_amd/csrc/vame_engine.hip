@@ -15,6 +15,7 @@
 
 #include "../../include/vame.h"
 #include "vame_kernel.h"
+#include "vame_mc_core.h"
 #include "vame_bipred.h"
 #include "vame_birefine.h"
 
@@ -1039,6 +1040,30 @@ int vame_affine_me(vame_ctx* c, const uint16_t* ref, const uint16_t* cur, float 
   return launch(c, std::vector<KParams>{kp}, align == 0, align == 1, align == 0, (hipStream_t)stream);
 }
 
+// The reference frames of a call into its parameter block: each non-null and
+// 4-byte aligned (the kernels read window rows as dwords).
+static bool set_refs(const uint16_t* (&dst)[4], const uint16_t* const* refs, int nrefs) {
+  for (int r = 0; r < nrefs; r++) {
+    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return false;
+    dst[r] = refs[r];
+  }
+  return true;
+}
+
+// The search's result arrays of refIdx 0 .. nrefs-1 for the PREDs in
+// `pred_mask` into a parameter block: each non-null.
+static bool set_result(const int64_t* (&cost)[4][4], const int32_t* (&cpmv)[4][4], const vame_poc_result* res,
+                       int nrefs, int pred_mask) {
+  for (int r = 0; r < nrefs; r++)
+    for (int m = 0; m < 4; m++) {
+      if (!((pred_mask >> m) & 1)) continue;
+      if (!res->cost[r][m] || !res->cpmvs[r][m]) return false;
+      cost[r][m] = res->cost[r][m];
+      cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
+    }
+  return true;
+}
+
 // vame_affine_mc (ncus_dev NULL) and vame_affine_mc_dev (ncus = the capacity)
 static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
                      const vame_mc_cu* cus, int ncus, const int32_t* ncus_dev, float lambda, uint16_t* pred,
@@ -1049,10 +1074,7 @@ static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* re
   if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
   McParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++) {
-    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
-    p.refs[r] = refs[r];
-  }
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
   if (ncus == 0) return VAME_OK;
   if (!cus) return VAME_E_INVALID;
   DeviceGuard guard(c->device);
@@ -1095,13 +1117,7 @@ int vame_partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_
   if (split_penalty < 0 || split_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
   PartParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++)
-    for (int m = 0; m < 4; m++) {
-      if (!((pred_mask >> m) & 1)) continue;
-      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
-      p.cost[r][m] = res->cost[r][m];
-      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
-    }
+  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
   DeviceGuard guard(c->device);
   VAME_HIP(guard.err);
   p.cus = reinterpret_cast<McCu*>(cus);
@@ -1130,10 +1146,7 @@ int vame_affine_mc_bi(vame_ctx* c, const uint16_t* cur, const uint16_t* const* r
   if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
   McBiParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++) {
-    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
-    p.refs[r] = refs[r];
-  }
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
   if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
   if (max_cus == 0) return VAME_OK;
   if (!cus) return VAME_E_INVALID;
@@ -1164,16 +1177,8 @@ int vame_bipred(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, i
   if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
   BiRowsParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++) {
-    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
-    p.refs[r] = refs[r];
-    for (int m = 0; m < 4; m++) {
-      if (!((pred_mask >> m) & 1)) continue;
-      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
-      p.cost[r][m] = res->cost[r][m];
-      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
-    }
-  }
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
   const bool on[2] = {(pred_mask & 3) != 0, (pred_mask & 12) != 0};
   for (int a = 0; a < 2; a++) {
     if (!on[a]) continue;
@@ -1213,13 +1218,7 @@ int vame_partition_bi(vame_ctx* c, const vame_poc_result* res, int nrefs, int pr
   if (bi_penalty < 0 || bi_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
   PartParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++)
-    for (int m = 0; m < 4; m++) {
-      if (!((pred_mask >> m) & 1)) continue;
-      if (!res->cost[r][m] || !res->cpmvs[r][m]) return VAME_E_INVALID;
-      p.cost[r][m] = res->cost[r][m];
-      p.cpmv[r][m] = reinterpret_cast<const int32_t*>(res->cpmvs[r][m]);
-    }
+  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
   for (int a = 0; a < 2; a++) {
     if (!((pred_mask >> (2 * a)) & 3)) continue;
     if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
@@ -1259,10 +1258,7 @@ int vame_bipred_refine(vame_ctx* c, const uint16_t* cur, const uint16_t* const* 
   if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
   BiRefineParams p;
   memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nrefs; r++) {
-    if (!refs[r] || (reinterpret_cast<uintptr_t>(refs[r]) & 3)) return VAME_E_INVALID;
-    p.refs[r] = refs[r];
-  }
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
   if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
   if (max_cus == 0) return VAME_OK;
   DeviceGuard guard(c->device);

@@ -2370,35 +2370,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
   X template __global__ void affine_me_half2w<1>(KParams); \
   X template __global__ void affine_me_half2h<1>(KParams);
 
-// ------------------------------------------- motion compensation (vame_mc.hip)
-// device view of vame_mc_cu (include/vame.h): 12 int32
-struct McCu {
-  int32_t x, y, w, h, ref;
-  int32_t ncps, ltx, lty, rtx, rty, lbx, lby;
-};
-constexpr int kMcMaxCus = 1 << 20;  // VAME_MC_MAX_CUS
-// int32 words of a context's scratch table: the offsets of kMcMaxCus
-// descriptors and the total, then the sums of the 1024 scan blocks
-constexpr size_t kMcScratchWords = (size_t)kMcMaxCus + 1 + 1024;
-struct McParams {
-  const uint16_t* cur;      // NULL when cost is
-  const uint16_t* refs[4];
-  const McCu* cus;
-  uint16_t* pred;           // or NULL
-  int64_t* cost;            // or NULL
-  int32_t* bad;
-  int32_t* offs;            // [ncus + 1]: first sub-block of each descriptor; the total
-  int32_t* blockSum;        // [1024]: sub-blocks per scan block
-  int ncus, nrefs, W, H;
-  float lambda;
-  // vame_affine_mc_dev: the count lives on the device, clamped to [0, ncus]
-  // (ncus sizes the grids); NULL: the count is ncus
-  const int32_t* ncusDev;
-};
-// The three launches of one vame_affine_mc call on `stream` (ncus >= 1).
-hipError_t mc_launch(const McParams& p, bool prof, hipStream_t stream);
-
 // ------------------------------------------- partition decision (vame_partition.hip)
+struct McCu;                      // the descriptor it emits (vame_mc_core.h)
 constexpr int kPartSlots = 1024;  // nodes of a CTU: ((lh*4 + lw)*8 + y/16)*8 + x/16
 // int32 words of a context's scratch per CTU: the leaf count, the leaf code of
 // each of the 64 top-left blocks, the owner of each of the 64 blocks

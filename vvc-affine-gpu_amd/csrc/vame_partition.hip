@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vame.h"
-#include "vame_kernel.h"
+#include "vame_mc_core.h"
 
 namespace vame {
 

@@ -99,6 +99,55 @@ class Engine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    # ---- argument checks shared by the prediction-side entry points
+    def _check_cus(self, t: torch.Tensor, cols: int, name: str = "cus", n: int | None = None) -> None:
+        """A descriptor tensor: contiguous int32 [n, cols] on the engine's device."""
+        if (t.dim() != 2 or t.shape[1] != cols or t.dtype != torch.int32 or t.device != self.device
+                or not t.is_contiguous() or (n is not None and t.shape[0] != n)):
+            raise ValueError(f"{name} must be a contiguous int32 [{'n' if n is None else n}, {cols}] tensor "
+                             f"on {self.device}")
+
+    def _refs(self, refs, what: str):
+        """1..4 reference frames: (the frames, their pointer array)."""
+        refs = [self._frame(r) for r in refs]
+        if not 1 <= len(refs) <= 4:
+            raise ValueError(f"{what} takes 1..4 reference frames")
+        return refs, (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
+
+    def _check_pred(self, pred: torch.Tensor | None) -> None:
+        if pred is not None and (pred.shape != (self.H, self.W) or pred.device != self.device
+                                 or pred.dtype not in (torch.int16, torch.uint16) or not pred.is_contiguous()):
+            raise ValueError(f"pred must be a contiguous ({self.H},{self.W}) int16/uint16 frame on {self.device}")
+
+    def _check_scalar(self, t: torch.Tensor | None, name: str) -> None:
+        if t is not None and (t.numel() != 1 or t.dtype != torch.int32 or t.device != self.device):
+            raise ValueError(f"{name} must be an int32 scalar on {self.device}")
+
+    def _check_part_out(self, out: dict, want: dict, cols: int) -> None:
+        """The tensors of a partition() (cols = 12) / partition_bi() (20) result
+        to write into: `want` holds the dtype of every key."""
+        shapes = {"cus": (self.n_ctus * 64, cols), "ctu_info": (self.n_ctus, 4), "ncus": (),
+                  "ctu_cost": (self.n_ctus,)}
+        for k, w in want.items():
+            t, shape = out[k], shapes.get(k, (self.n_ctus * 64,))
+            if tuple(t.shape) != shape or t.dtype != w.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {w.dtype} {shape} tensor on {self.device}")
+
+    def _mc_checks(self, what: str, cols: int, cus, refs, cur, pred, want_cost: bool, ncus):
+        """The argument checks of affine_mc (cols = 12) and affine_mc_bi (20), in
+        their order: (cur or None, the reference pointers, nrefs)."""
+        self._check_cus(cus, cols)
+        if pred is None and not want_cost:
+            raise ValueError(f"{what} needs pred, want_cost or both")
+        refs, ref_ptrs = self._refs(refs, what)
+        if want_cost:
+            if cur is None:
+                raise ValueError("want_cost needs cur")
+            cur = self._frame(cur)
+        self._check_pred(pred)
+        self._check_scalar(ncus, "ncus")
+        return cur if want_cost else None, ref_ptrs, len(refs)
+
     def _check_out(self, out, align: int):
         """Caller-supplied result buffers must hold exactly the launch's rows:
         int64 cost[n], int32 cpmv[n, 7], contiguous, on the engine's device."""
@@ -223,34 +272,16 @@ class Engine:
         number of descriptors to run (vame_affine_mc_dev: min(ncus, n), read on
         the device; rows of cus and cost past it are neither read nor
         written).  Asynchronous on the current stream."""
-        if (cus.dim() != 2 or cus.shape[1] != 12 or cus.dtype != torch.int32 or cus.device != self.device
-                or not cus.is_contiguous()):
-            raise ValueError(f"cus must be a contiguous int32 [n, 12] tensor on {self.device}")
-        if pred is None and not want_cost:
-            raise ValueError("affine_mc needs pred, want_cost or both")
-        refs = [self._frame(r) for r in refs]
-        if not 1 <= len(refs) <= 4:
-            raise ValueError("affine_mc takes 1..4 reference frames")
-        if want_cost:
-            if cur is None:
-                raise ValueError("want_cost needs cur")
-            cur = self._frame(cur)
-        if pred is not None and (pred.shape != (self.H, self.W) or pred.device != self.device
-                                 or pred.dtype not in (torch.int16, torch.uint16) or not pred.is_contiguous()):
-            raise ValueError(f"pred must be a contiguous ({self.H},{self.W}) int16/uint16 frame on {self.device}")
+        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc", 12, cus, refs, cur, pred, want_cost, ncus)
         n = cus.shape[0]
         cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
         if ncus is not None:
-            if ncus.numel() != 1 or ncus.dtype != torch.int32 or ncus.device != self.device:
-                raise ValueError(f"ncus must be an int32 scalar on {self.device}")
-            check(lib().vame_affine_mc_dev(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs),
-                                           _ptr(cus), n, _ptr(ncus), float(lam), _ptr(pred), _ptr(cost), _ptr(bad),
-                                           self._stream()))
-            return pred, cost, bad
-        check(lib().vame_affine_mc(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs), _ptr(cus), n,
-                                   float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+            check(lib().vame_affine_mc_dev(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, _ptr(ncus), float(lam),
+                                           _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+        else:
+            check(lib().vame_affine_mc(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, float(lam), _ptr(pred),
+                                       _ptr(cost), _ptr(bad), self._stream()))
         return pred, cost, bad
 
     def partition(self, result: dict, preds: int | None = None, split_penalty: int = 0, out: dict | None = None):
@@ -283,14 +314,7 @@ class Engine:
                         raise ValueError(f"result buffers missing for {(r, name)}")
                     self._check_out(result[(r, name)], m >> 1)
         if out is not None:
-            want = P.alloc(0, "cpu")
-            for k in P.KEYS:
-                t = out[k]
-                shape = (self.n_ctus * 64, 12) if k == "cus" else (self.n_ctus, 4) if k == "ctu_info" else \
-                    () if k == "ncus" else (self.n_ctus,) if k == "ctu_cost" else (self.n_ctus * 64,)
-                if (tuple(t.shape) != shape or t.dtype != want[k].dtype or t.device != self.device
-                        or not t.is_contiguous()):
-                    raise ValueError(f"out[{k!r}] must be a contiguous {want[k].dtype} {shape} tensor on {self.device}")
+            self._check_part_out(out, P.alloc(0, "cpu"), 12)
         return P.partition(self._h, self.n_ctus, self.device, result, preds, split_penalty, self._stream(), out)
 
     def predict_partition(self, part: dict, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
@@ -351,29 +375,12 @@ class Engine:
         exactly affine_mc; else the sample is the once-rounded average of the
         two hypotheses and the cost carries both rates.  Arguments and the
         returned (pred, cost, bad) as affine_mc.  Not available under PROF."""
-        if (cus.dim() != 2 or cus.shape[1] != 20 or cus.dtype != torch.int32 or cus.device != self.device
-                or not cus.is_contiguous()):
-            raise ValueError(f"cus must be a contiguous int32 [n, 20] tensor on {self.device}")
-        if pred is None and not want_cost:
-            raise ValueError("affine_mc_bi needs pred, want_cost or both")
-        refs = [self._frame(r) for r in refs]
-        if not 1 <= len(refs) <= 4:
-            raise ValueError("affine_mc_bi takes 1..4 reference frames")
-        if want_cost:
-            if cur is None:
-                raise ValueError("want_cost needs cur")
-            cur = self._frame(cur)
-        if pred is not None and (pred.shape != (self.H, self.W) or pred.device != self.device
-                                 or pred.dtype not in (torch.int16, torch.uint16) or not pred.is_contiguous()):
-            raise ValueError(f"pred must be a contiguous ({self.H},{self.W}) int16/uint16 frame on {self.device}")
-        if ncus is not None and (ncus.numel() != 1 or ncus.dtype != torch.int32 or ncus.device != self.device):
-            raise ValueError(f"ncus must be an int32 scalar on {self.device}")
+        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc_bi", 20, cus, refs, cur, pred, want_cost, ncus)
         n = cus.shape[0]
         cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
-        check(lib().vame_affine_mc_bi(self._h, _ptr(cur) if want_cost else None, ref_ptrs, len(refs), _ptr(cus), n,
-                                      _ptr(ncus), float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+        check(lib().vame_affine_mc_bi(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, _ptr(ncus), float(lam),
+                                      _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
         return pred, cost, bad
 
     def bipred(self, cur, refs, lam: float, result: dict, preds: int | None = None, out: dict | None = None):
@@ -388,9 +395,7 @@ class Engine:
         from . import bipred as B
         from . import partition as P
         cur = self._frame(cur)
-        refs = [self._frame(r) for r in refs]
-        if not 1 <= len(refs) <= 4:
-            raise ValueError("bipred takes 1..4 reference frames")
+        refs, ref_ptrs = self._refs(refs, "bipred")
         if not result:
             raise ValueError("bipred needs a result dict")
         preds = P.result_preds(result) if preds is None else int(preds)
@@ -403,7 +408,6 @@ class Engine:
             full = B.alloc_bi(self.n_ctus, self.device)
             out = {k: [t if (preds >> (2 * a)) & 3 else None for a, t in enumerate(full[k])] for k in ("cost", "sel")}
         cost, sel = self._check_bi(out, preds)
-        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
         check(lib().vame_bipred(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds,
                                 cost, sel, self._stream()))
         return out
@@ -426,16 +430,9 @@ class Engine:
             raise ValueError("split_penalty and bi_penalty must be in [0, 2^40]")
         nrefs, pr = self._check_result(result, preds, "partition_bi")
         bcost, bsel = self._check_bi(bi, preds)
-        want = B.alloc(0, "cpu")
         if out is None:
             out = B.alloc(self.n_ctus, self.device)
-        for k in B.KEYS:
-            t = out[k]
-            shape = (self.n_ctus * 64, 20) if k == "cus" else (self.n_ctus, 4) if k == "ctu_info" else \
-                () if k == "ncus" else (self.n_ctus,) if k == "ctu_cost" else (self.n_ctus * 64,)
-            if (tuple(t.shape) != shape or t.dtype != want[k].dtype or t.device != self.device
-                    or not t.is_contiguous()):
-                raise ValueError(f"out[{k!r}] must be a contiguous {want[k].dtype} {shape} tensor on {self.device}")
+        self._check_part_out(out, B.alloc(0, "cpu"), 20)
         V = ctypes.c_void_p
         check(lib().vame_partition_bi(self._h, ctypes.byref(pr), nrefs, preds, int(split_penalty), bcost, bsel,
                                       int(bi_penalty), *(V(out[k].data_ptr()) for k in B.KEYS), self._stream()))
@@ -456,31 +453,23 @@ class Engine:
         an int32 scalar on the device, the number of descriptors to work on
         (entries past it stay untouched); out may be cus.  Reads nothing on the
         host; asynchronous on the current stream.  Not available under PROF."""
-        def bad_cus(t):
-            return (t.dim() != 2 or t.shape[1] != 20 or t.dtype != torch.int32 or t.device != self.device
-                    or not t.is_contiguous())
-        if bad_cus(cus):
-            raise ValueError(f"cus must be a contiguous int32 [n, 20] tensor on {self.device}")
+        self._check_cus(cus, 20)
         if not 0 <= int(rounds) <= 4:
             raise ValueError("rounds must be in 0..4")
-        refs = [self._frame(r) for r in refs]
-        if not 1 <= len(refs) <= 4:
-            raise ValueError("bipred_refine takes 1..4 reference frames")
+        refs, ref_ptrs = self._refs(refs, "bipred_refine")
         cur = self._frame(cur)
         n = cus.shape[0]
-        if count is not None and (count.numel() != 1 or count.dtype != torch.int32 or count.device != self.device):
-            raise ValueError(f"count must be an int32 scalar on {self.device}")
+        self._check_scalar(count, "count")
         if out is None:
             out = torch.empty_like(cus)
-        elif bad_cus(out) or out.shape[0] != n:
-            raise ValueError(f"out must be a contiguous int32 [{n}, 20] tensor on {self.device}")
+        else:
+            self._check_cus(out, 20, "out", n)
         if cost is None:
             cost = torch.empty(n, dtype=torch.int64, device=self.device)
         elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
               or not cost.is_contiguous()):
             raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
         check(lib().vame_bipred_refine(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(count),
                                        float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
         return out, cost, bad

@@ -334,10 +334,14 @@ int vame_set_prof(vame_ctx* ctx, int enable);
 /* Device-side kernel timing (the reference's per-PRED kernelExecutionTime,
  * main.cpp:856-866): when enabled, every kernel launch carries hipEvents in its
  * own dispatch on the stream it runs on.  kernel_class 0 = quadrant work items
- * (affine_me_quad); 3 = the 128x128 CUs (affine_me_ctu2); 4 / 5 = the 128x64 /
- * 64x128 CUs (affine_me_half2w / _half2h); under PROF 1 = the 128x128 CUs
- * (affine_me_ctu_prof), 2 = the 128x64 / 64x128 CUs (affine_me_half_prof).
- * enable = 2 times the quadrant kernel only (its dispatches carry the events;
+ * (affine_me_quad); 6 = those of 32 to 128 sub-blocks in launches with 3-CP
+ * (affine_me_quad2; 2-CP-only launches run them in affine_me_quad); 3 = the
+ * 128x128 CUs (affine_me_ctu2); 4 / 5 = the 128x64 / 64x128 CUs
+ * (affine_me_half2w / _half2h) -- in 2-CP-only launches 4 = both, in one
+ * affine_me_half2 launch, and 5 stays empty; under PROF 0 = every quadrant
+ * work item (affine_me_quad_prof), 1 = the 128x128 CUs (affine_me_ctu_prof),
+ * 2 = the 128x64 / 64x128 CUs (affine_me_half_prof).
+ * enable = 2 times the quadrant kernels only (their dispatches carry the events;
  * the 128-class launches run untimed).  vame_get_timing waits for the recorded
  * launches and returns their summed duration and count since the last reset.
  * enable | VAME_TIMING_KEEP changes what later launches record without

@@ -251,7 +251,7 @@ def test_live_reference_configs(engines, tmp_path, W, H, qp, poc, refidx, extra)
 def test_live_reference_c2_step_2cp_only(engines, tmp_path):
     """the benchmarked kernels themselves -- the 2-CP-only
     instantiations (MODE 1: affine_me_quad<1>, affine_me_ctu2<1>,
-    affine_me_half2w<1> / _half2h<1>) -- against the reference kernels built
+    affine_me_half2<1>) -- against the reference kernels built
     with -DnCP=2 (affine.cl:11 / :960, main.cpp:389-392), launched as
     FULL_2CP + HALF_2CP only (REF_PRED_MASK = 5): the c2 step exactly as
     bench.py codes it (1920x1080 QP32, POCs 1 and 2 of the bench's sequence in
@@ -726,3 +726,87 @@ def test_pack_records_equals_shard_pack(engines, modes):
     bad.zero_()
     eng.pack_records(res, modes, None, bad)
     assert int(bad) == 1
+
+
+def _tensors(res):
+    """The tensors of a result: an alloc_poc dict, or one (cost, cpmv) pair."""
+    pairs = [res[k] for k in sorted(res)] if isinstance(res, dict) else [res]
+    return [t for pair in pairs for t in pair]
+
+
+def _poc(modes, prof=False):
+    def call(eng, cur, ref, lam, extra):
+        eng.set_prof(prof)
+        try:
+            return eng.affine_me_poc(cur, [ref], lam, modes=modes, extra=extra)
+        finally:
+            eng.set_prof(False)
+    return call
+
+
+def _dropin(align, ncp):
+    def call(eng, cur, ref, lam, extra):
+        prev = None
+        if ncp == 3:  # its seed: the 2-CP launch, not counted
+            prev = eng.affine_me(ref, cur, lam, align, 2, extra)[1]
+            for cls in range(7):
+                eng.get_timing(cls, reset=True)
+        return eng.affine_me(ref, cur, lam, align, ncp, extra, prev=prev)
+    return call
+
+
+def _batch_one_pair_per_launch(eng, cur, ref, lam, extra):
+    eng.set_max_pairs(1)
+    return eng.affine_me_batch([(cur, [ref, ref], lam, eng.alloc_poc(2, 3))], 3, extra)[0]
+
+
+# The dispatches of one call, as vame_get_timing counts them per timing class
+# 0..6 (include/vame.h): (call, context's environment, launches of each class).
+LAUNCH_TABLE = {
+    "poc_2cp": (_poc(1), {}, (1, 0, 0, 1, 1, 0, 0)),
+    "poc_23cp": (_poc(3), {}, (1, 0, 0, 1, 1, 1, 1)),
+    "poc_23cp_full": (_poc(3 | 4), {}, (1, 0, 0, 1, 1, 1, 1)),
+    "poc_2cp_half": (_poc(1 | 8), {}, (1, 0, 0, 0, 0, 0, 0)),
+    "poc_23cp_half": (_poc(3 | 8), {}, (1, 0, 0, 0, 0, 0, 1)),
+    "prof_23cp": (_poc(3, prof=True), {}, (1, 1, 1, 0, 0, 0, 0)),
+    "dropin_full_3cp": (_dropin(0, 3), {}, (1, 0, 0, 1, 1, 1, 1)),
+    "dropin_half_2cp": (_dropin(1, 2), {}, (1, 0, 0, 0, 0, 0, 0)),
+    "batch_two_refs_one_pair_per_launch": (_batch_one_pair_per_launch, {}, (2, 0, 0, 2, 2, 2, 2)),
+    "poc_2cp_one_stream": (_poc(1), {"VAME_STREAMS": "1"}, (1, 0, 0, 1, 1, 0, 0)),
+    "poc_23cp_one_stream": (_poc(3), {"VAME_STREAMS": "1"}, (1, 0, 0, 1, 1, 1, 1)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(LAUNCH_TABLE))
+def test_launch_table(engines, case, monkeypatch):
+    """Which kernels a call dispatches, by timing class: a 2-CP-only call runs
+    affine_me_quad, affine_me_ctu2 and the merged affine_me_half2 (classes 0,
+    3, 4); a call with 3-CP affine_me_quad2, affine_me_quad, affine_me_ctu2,
+    affine_me_half2w and affine_me_half2h (6, 0, 3, 4, 5); PROF its three
+    kernels (0, 1, 2); a HALF-only call the quadrant kernels alone; a batch of
+    two launches each kernel twice; one stream or two, the same.  Every other
+    class reads 0.  The timed call's results equal the default context's
+    untimed ones bit for bit."""
+    from vame.engine import Engine
+    call, env, want = LAUNCH_TABLE[case]
+    z = np.load(GOLDEN[0])
+    W, H, lam, extra = int(z["W"]), int(z["H"]), float(z["lam"]), int(z["extra"])
+    assert (W, H) == (416, 240)
+    cur, ref = dev(z["cur"]), dev(z["ref"])
+    base = engines(W, H)
+    base.set_timing(False)
+    ref_out = _tensors(call(base, cur, ref, lam, extra))
+    base.set_max_pairs(32)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    eng = Engine(W, H, 0)
+    try:
+        eng.set_timing(True)
+        out = _tensors(call(eng, cur, ref, lam, extra))
+        torch.cuda.synchronize()
+        got = tuple(eng.get_timing(cls)[1] for cls in range(7))
+        print(case, "launches of classes 0..6:", got)
+        assert got == want
+        assert len(out) == len(ref_out) and all(torch.equal(a, b) for a, b in zip(out, ref_out))
+    finally:
+        eng.close()

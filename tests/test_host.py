@@ -197,10 +197,19 @@ def test_product_kernels_have_no_scratch():
     back fails here: the quadrant kernels (affine_me_quad, affine_me_quad2, the
     bulk of every step) have a zero private segment, the 128-class ones at most
     8 B per lane (one slot in affine_me_ctu2<2>, affine_me_half2w/h<2,3>); the
-    PROF variants are not the benchmarked path."""
+    PROF variants are not the benchmarked path.  The library holds exactly
+    the 13 instances the engine launches, (kernel, MODE): a kernel that nothing
+    launches is a stray instantiation."""
     sizes = kernel_scratch(_lib.LIB_PATH)
     product = {k: v for k, v in sizes.items() if "affine_me" in k and "prof" not in k}
-    assert len(product) == 16, sorted(product)
+    # _ZN4vame<len><kernel>ILi<MODE>EEEvNS_7KParamsE
+    got = {(m.group(1), int(m.group(2))): k
+           for k in product for m in [re.fullmatch(r"_ZN4vame\d+(affine_me_\w+?)ILi(\d)EEEvNS_7KParamsE", k)] if m}
+    assert len(got) == len(product), sorted(product)
+    want = ({("affine_me_quad", m) for m in (1, 2, 3)} | {("affine_me_quad2", m) for m in (2, 3)}
+            | {("affine_me_ctu2", m) for m in (1, 2, 3)} | {("affine_me_half2", 1)}
+            | {("affine_me_half2w", m) for m in (2, 3)} | {("affine_me_half2h", m) for m in (2, 3)})
+    assert set(got) == want and len(want) == 13, sorted(set(got) ^ want)
     for k, v in product.items():
         if "affine_me_quad" in k:
             assert v == 0, (k, v)

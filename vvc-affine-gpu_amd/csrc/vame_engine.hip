@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vame.h"
@@ -56,8 +57,8 @@ struct vame_ctx {
   // CU one sub-block per lane, affine_me_quad_prof); and the 128-class CUs,
   // each a workgroup of its own: the 128x128 CU (dBig1: affine_me_ctu2;
   // affine_me_ctu_prof under PROF) and every 128x64 / 64x128 CU (dHalfW /
-  // dHalfH: affine_me_half2w / _half2h; both in dHalf for affine_me_half_prof
-  // under PROF)
+  // dHalfH, adjacent: affine_me_half2w / _half2h, or both in one
+  // affine_me_half2 launch; both in dHalf for affine_me_half_prof under PROF)
   Item* dQuad = nullptr;
   int quadOff[4][3] = {}, quadN[4][3] = {};
   Item* dBig1 = nullptr;
@@ -94,8 +95,7 @@ struct vame_ctx {
   // the barrier bit, the others after it in any order.
   int streams = 2;
   hipStream_t side = nullptr;
-  hipStream_t side2 = nullptr;  // timing builds VAME_Q1_SIDE=2: affine_me_quad on a stream of its own
-  hipEvent_t evFork = nullptr, evJoin = nullptr, evJoin2 = nullptr;
+  hipEvent_t evFork = nullptr, evJoin = nullptr;
   // VAME_SYNC (default 1): the join as a stream memory operation -- the side
   // stream writes a sequence number to a signal-memory word
   // (hipStreamWriteValue32, ordered after its earlier work), the caller's
@@ -112,7 +112,8 @@ struct vame_ctx {
   // optional per-kernel timing: (start, end) event pairs per kernel class
   // (0 affine_me_quad, 1 128x128 CUs in affine_me_ctu_prof, 2 128x64 / 64x128
   // CUs in affine_me_half_prof, 3 128x128 CUs in affine_me_ctu2, 4 / 5 128x64 /
-  // 64x128 CUs in affine_me_half2w / _half2h, 6 affine_me_quad2)
+  // 64x128 CUs in affine_me_half2w / _half2h -- 4 both, in affine_me_half2, in
+  // 2-CP-only launches --, 6 affine_me_quad2)
   int timing = 0;
   // PROF on (vame_set_prof): the *_prof kernels
   bool prof = false;
@@ -270,11 +271,7 @@ Item make_auto_item(int rx, int ry, const std::vector<std::vector<CuDesc>>& task
 // CUs of one quadrant: wave tasks of one size class (largest first, at most
 // kTaskCu CUs and 64 lanes each), then items of kMaxTasks consecutive tasks.
 // Returns the number of items appended.
-#ifndef VAME_Q2_TASKS  // timing builds: wave tasks per affine_me_quad2 item
-#define VAME_Q2_TASKS 16
-#endif
 size_t pack_autonomous(int qx, int qy, std::vector<CuDesc> cus, std::vector<Item>& out, int sbl) {
-  const int perItem = sbl == 2 ? VAME_Q2_TASKS : kMaxTasks;
   std::stable_sort(cus.begin(), cus.end(),
                    [](const CuDesc& a, const CuDesc& b) { return nsb_of(a) > nsb_of(b); });
   std::vector<std::vector<CuDesc>> waves;
@@ -284,12 +281,12 @@ size_t pack_autonomous(int qx, int qy, std::vector<CuDesc> cus, std::vector<Item
       waves.push_back({});
     waves.back().push_back(c);
   }
-  for (size_t w = 0; w < waves.size(); w += perItem) {
+  for (size_t w = 0; w < waves.size(); w += kMaxTasks) {
     std::vector<std::vector<CuDesc>> grp(waves.begin() + w,
-                                         waves.begin() + std::min(waves.size(), w + perItem));
+                                         waves.begin() + std::min(waves.size(), w + kMaxTasks));
     out.push_back(make_auto_item(qx, qy, grp, sbl));
   }
-  return (waves.size() + perItem - 1) / perItem;
+  return (waves.size() + kMaxTasks - 1) / kMaxTasks;
 }
 
 // The quadrant items of one kernel: for launches of FULL CUs only, HALF CUs
@@ -534,51 +531,31 @@ std::vector<int32_t> build_order(int nCtus, int cols, int groupCombos, int& nChu
   return order;
 }
 
-// The kernel instance of a launch mode (vame_kernel.h MODE: 1 = 2-CP only,
-// 2 = 3-CP only, 3 = 2-CP then 3-CP).
+// The kernel instances by launch mode (vame_kernel.h MODE: 1 = 2-CP only,
+// 2 = 3-CP only, 3 = 2-CP then 3-CP), at [MODE - 1]; nullptr: the launch plan
+// never runs the kernel in that mode, so no instance of it is built.  A
+// 2-CP-only launch runs the SBL1 and SBL2 quadrant items in one affine_me_quad
+// kernel (the short c2 step needs the two kinds of items side by side: 0.889
+// vs 0.953 ms as two kernels) and the 128x64 and 64x128 CUs in one
+// affine_me_half2 launch (c2 0.883 vs 0.888 ms); the other modes run
+// affine_me_quad2 beside affine_me_quad (c4 291.3 vs 298.8 ms in one kernel,
+// whose two bodies spill 104 vs 28 B per lane) and affine_me_half2w then
+// affine_me_half2h (c4 290.9 vs 292.5 ms merged: 88 vs 20 B per lane),
+// profiles/r06_quad2_ab.txt.
 using KernelFn = void (*)(KParams);
-// the 128x64 and 64x128 CUs in one launch (affine_me_half2) in 2-CP-only
-// launches (c2 0.883 vs 0.888 ms), affine_me_half2w then affine_me_half2h in
-// the others (c4 290.9 vs 292.5 ms: the merged kernel's two bodies spill 88 vs
-// 20 B per lane), profiles/r06_quad2_ab.txt.  Timing builds: VAME_HALF_MERGE=2
-// merged in every mode, 0 in none.
-#ifndef VAME_HALF_MERGE
-#define VAME_HALF_MERGE 1
-#endif
-inline bool half_merged(int mode) { return VAME_HALF_MERGE == 2 || (VAME_HALF_MERGE == 1 && mode == 1); }
-
-template <int KIND>
-KernelFn kernel_for(int mode) {
-  if constexpr (KIND == kKindHalf2W) {
-    return mode == 1 ? affine_me_half2w<1> : mode == 2 ? affine_me_half2w<2> : affine_me_half2w<3>;
-  } else if constexpr (KIND == kKindHalf2H) {
-    return mode == 1 ? affine_me_half2h<1> : mode == 2 ? affine_me_half2h<2> : affine_me_half2h<3>;
-  } else if constexpr (KIND == kKindCtu2) {
-    return mode == 1 ? affine_me_ctu2<1> : mode == 2 ? affine_me_ctu2<2> : affine_me_ctu2<3>;
-  } else if constexpr (KIND == kKindQuad2) {
-    return mode == 1 ? affine_me_quad2<1> : mode == 2 ? affine_me_quad2<2> : affine_me_quad2<3>;
-  } else if constexpr (KIND == kKindHalf2W + 100) {  // both orientations (affine_me_half2)
-    if constexpr (VAME_HALF_MERGE == 2)
-      return mode == 1 ? affine_me_half2<1> : mode == 2 ? affine_me_half2<2> : affine_me_half2<3>;
-    else
-      return mode == 1 ? affine_me_half2<1> : nullptr;  // half_merged(): 2-CP-only launches
-  } else if constexpr (KIND == kKindCtu) {  // PROF only
-    return mode == 1 ? affine_me_ctu_prof<1> : mode == 2 ? affine_me_ctu_prof<2> : affine_me_ctu_prof<3>;
-  } else if constexpr (KIND == kKindHalf) {  // PROF only
-    return mode == 1 ? affine_me_half_prof<1> : mode == 2 ? affine_me_half_prof<2> : affine_me_half_prof<3>;
-  } else {
-    return mode == 1 ? affine_me_quad<1> : mode == 2 ? affine_me_quad<2> : affine_me_quad<3>;
-  }
-}
-KernelFn quad_kernel(bool prof, int mode) {
-  if (prof) return mode == 1 ? affine_me_quad_prof<1> : mode == 2 ? affine_me_quad_prof<2> : affine_me_quad_prof<3>;
-  return kernel_for<kKindQuad>(mode);
-}
+constexpr KernelFn kQuadProf[3] = {affine_me_quad_prof<1>, affine_me_quad_prof<2>, affine_me_quad_prof<3>};
+constexpr KernelFn kQuad[3] = {affine_me_quad<1>, affine_me_quad<2>, affine_me_quad<3>};
+constexpr KernelFn kCtuProf[3] = {affine_me_ctu_prof<1>, affine_me_ctu_prof<2>, affine_me_ctu_prof<3>};
+constexpr KernelFn kCtu2[3] = {affine_me_ctu2<1>, affine_me_ctu2<2>, affine_me_ctu2<3>};
+constexpr KernelFn kHalfProf[3] = {affine_me_half_prof<1>, affine_me_half_prof<2>, affine_me_half_prof<3>};
+constexpr KernelFn kHalf2H[3] = {nullptr, affine_me_half2h<2>, affine_me_half2h<3>};
+constexpr KernelFn kHalf2W[3] = {nullptr, affine_me_half2w<2>, affine_me_half2w<3>};
+constexpr KernelFn kQuad2[3] = {nullptr, affine_me_quad2<2>, affine_me_quad2<3>};
+constexpr KernelFn kHalf2[3] = {affine_me_half2<1>, nullptr, nullptr};
 
 // Launch one kernel: with the dispatch-carried timing events and AQL flags, or
 // (the caller's stream under capture) as a plain launch, which the graph records.
-template <typename K>
-hipError_t launch_kernel(K kernel, unsigned grid, unsigned threads, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
+hipError_t launch_kernel(KernelFn kernel, unsigned grid, unsigned threads, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
                          int flags, const KParams& kp, bool capture) {
   if (grid == 0) return hipSuccess;  // no work items (a kernel class without CUs)
   if (capture)
@@ -588,22 +565,93 @@ hipError_t launch_kernel(K kernel, unsigned grid, unsigned threads, hipStream_t 
   return hipGetLastError();
 }
 
+// One dispatch of a launch: the kernel, its work items and where it runs.
+struct Dispatch {
+  KernelFn kernel;
+  unsigned threads;
+  const Item* items;
+  int nItems;
+  int32_t* bestS;  // the kernel's region of the seed-reuse sums, or nullptr
+  int order;       // block-order class (block_grid)
+  int timing;      // timing class (vame_ctx::timing)
+  bool side;       // on the quadrant stream: the side stream of a forked call
+};
 
-// where affine_me_quad runs beside the 128-class kernels (VAME_Q1_SIDE
-// timing builds: 1 = after affine_me_quad2 on the quadrant stream)
-#ifndef VAME_Q1_SIDE
-#define VAME_Q1_SIDE 0
-#endif
-constexpr bool kQ1Side = VAME_Q1_SIDE == 1;  // 2: on a second side stream
-// The quadrant kernels, by launch mode (default, VAME_SPLIT=3, vame_kernel.h
-// kQuadMerged): a 2-CP-only launch runs one affine_me_quad kernel over the
-// SBL1 and SBL2 items (the short c2 step needs the two kinds of items side by
-// side: c2 0.889 vs 0.953 ms as two kernels), a 2+3-CP launch the SBL2 items
-// in affine_me_quad2 on the quadrant stream beside affine_me_quad with the
-// SBL1 items on the caller's stream (c4 291.3 vs 298.8 ms in one kernel, whose
-// two bodies spill more: 104 vs 28 B per lane), profiles/r06_quad2_ab.txt.
-// Timing builds: 2 / 1 one structure for every mode, 0 every quadrant CU one
-// sub-block per lane (the packing of rounds 4-5, which PROF keeps).
+// The dispatches of one launch in issue order, at most six; returns their
+// number.  The quadrant kernels: affine_me_quad_prof over item set 2 under
+// PROF, affine_me_quad over set 3 in a 2-CP-only launch, else affine_me_quad2
+// (set 1) on the quadrant stream and affine_me_quad (set 0) on the caller's.
+// The 128-class kernels (bigItems), all on the caller's stream: the 128x128
+// CUs, then the 128x64 and 64x128 CUs.  A forked call issues the 128-class
+// kernels first, a call on one stream the quadrant kernels.
+int launch_plan(const vame_ctx* c, int mode, bool quadFull, bool quadHalf, bool bigItems, bool fork,
+                Dispatch (&plan)[6]) {
+  const int m = mode - 1, aset = quadFull && quadHalf ? 2 : quadFull ? 0 : 1;
+  const auto quad = [&](KernelFn k, int set, int timing, bool side) {
+    return Dispatch{k, Cfg<kKindQuad>::THREADS, c->dQuad + c->quadOff[set][aset], c->quadN[set][aset],
+                    c->bestS + c->bestOff[3], 0, timing, side};
+  };
+  const auto big = [&](KernelFn k, unsigned threads, const Item* items, int nItems, int region, int timing) {
+    return Dispatch{k, threads, items, nItems, region < 0 ? nullptr : c->bestS + c->bestOff[region], 1, timing, false};
+  };
+  Dispatch q[2], b[3];
+  int nq = 0, nb = 0;
+  if (quadFull || quadHalf) {
+    if (c->prof) {
+      q[nq++] = quad(kQuadProf[m], 2, 0, true);
+    } else if (mode == 1) {
+      q[nq++] = quad(kQuad[m], 3, 0, true);
+    } else {
+      q[nq++] = quad(kQuad2[m], 1, 6, true);
+      q[nq++] = quad(kQuad[m], 0, 0, false);
+    }
+  }
+  if (bigItems) {
+    if (c->prof) {
+      b[nb++] = big(kCtuProf[m], Cfg<kKindCtu>::THREADS, c->dBig1, c->nBig1, 0, 1);
+      b[nb++] = big(kHalfProf[m], Cfg<kKindHalf>::THREADS, c->dHalf, c->nHalf, -1, 2);
+    } else {
+      b[nb++] = big(kCtu2[m], Cfg<kKindCtu2>::THREADS, c->dBig1, c->nBig1, 0, 3);
+      if (mode == 1) {  // both orientations, dHalfW then dHalfH: the two regions' span
+        b[nb++] = big(kHalf2[m], Cfg<kKindHalf2W>::THREADS, c->dHalfW, c->nHalfW + c->nHalfH, 1, 4);
+      } else {
+        b[nb++] = big(kHalf2W[m], Cfg<kKindHalf2W>::THREADS, c->dHalfW, c->nHalfW, 1, 4);
+        b[nb++] = big(kHalf2H[m], Cfg<kKindHalf2H>::THREADS, c->dHalfH, c->nHalfH, 2, 5);
+      }
+    }
+  }
+  Dispatch* end = plan;
+  if (fork) end = std::copy(b, b + nb, end);
+  end = std::copy(q, q + nq, end);
+  if (!fork) end = std::copy(b, b + nb, end);
+  return (int)(end - plan);
+}
+
+// The join of a forked call: the caller's stream waits for the side stream.
+int join_side(vame_ctx* c, hipStream_t stream, bool capture) {
+  if (c->valueSync != 0 && c->syncWord && !capture) {
+    const uint32_t v = ++c->joinSeq;
+    VAME_HIP(hipStreamWriteValue32(c->side, c->syncWord, v, 0));
+    VAME_HIP(hipStreamWaitValue32(stream, c->syncWord, v, hipStreamWaitValueGte, 0xFFFFFFFFu));
+  } else {
+    VAME_HIP(hipEventRecord(c->evJoin, c->side));
+    VAME_HIP(hipStreamWaitEvent(stream, c->evJoin, 0));
+  }
+  return VAME_OK;
+}
+
+// One dispatch for the pairs of kp on stream s.
+int dispatch(vame_ctx* c, const Dispatch& d, const KParams& kp, hipStream_t s, int flags, bool capture) {
+  KParams k = kp;
+  k.items = d.items;
+  k.nItems = d.nItems;
+  k.bestS = d.bestS;
+  const unsigned grid = block_grid(c, d.order, k);
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  if (!capture) VAME_TRY(time_events(c, d.timing, t0, t1));
+  VAME_HIP(launch_kernel(d.kernel, grid, d.threads, s, t0, t1, flags, k, capture));
+  return VAME_OK;
+}
 
 // The launches of one call.  By default (VAME_STREAMS=2) the 128-class
 // kernels run on the caller's stream and the quadrant kernel on a side stream
@@ -625,146 +673,27 @@ int launch_direct(vame_ctx* c, const std::vector<KParams>& kps, bool quadFull, b
   const int mode = (kps[0].run2 ? 1 : 0) | (kps[0].run3 ? 2 : 0);  // the kernel instance (MODE)
   if (mode == 0) return VAME_OK;
   const bool fork = c->streams == 2 && bigItems && (quadFull || quadHalf);
-  const hipStream_t sQuad = fork ? c->side : stream;
   if (fork && !c->side) return VAME_E_INVALID;
-  int issued = 0;  // VAME_STREAMS=1: kernels after a call's first may start before it ends
-  auto order_flag = [&]() { return c->streams == 1 && issued++ > 0 ? hipExtAnyOrderLaunch : 0; };
-  const bool valueSync = c->valueSync != 0 && c->syncWord && !capture;
-  auto events = [&](int cls, hipEvent_t& t0, hipEvent_t& t1) -> int {
-    t0 = t1 = nullptr;
-    return capture ? VAME_OK : time_events(c, cls, t0, t1);
-  };
-  auto join = [&]() -> int {
-    if (valueSync) {
-      const uint32_t v = ++c->joinSeq;
-      VAME_HIP(hipStreamWriteValue32(c->side, c->syncWord, v, 0));
-      VAME_HIP(hipStreamWaitValue32(stream, c->syncWord, v, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    } else {
-      VAME_HIP(hipEventRecord(c->evJoin, c->side));
-      VAME_HIP(hipStreamWaitEvent(stream, c->evJoin, 0));
-    }
-    if (c->side2) {
-      VAME_HIP(hipEventRecord(c->evJoin2, c->side2));
-      VAME_HIP(hipStreamWaitEvent(stream, c->evJoin2, 0));
-    }
-    return VAME_OK;
-  };
+  Dispatch plan[6];
+  const int n = launch_plan(c, mode, quadFull, quadHalf, bigItems, fork, plan);
   if (fork) {
     VAME_HIP(hipEventRecord(c->evFork, stream));
     VAME_HIP(hipStreamWaitEvent(c->side, c->evFork, 0));
-    if (c->side2) VAME_HIP(hipStreamWaitEvent(c->side2, c->evFork, 0));
   }
-  // the 128x128 CUs: affine_me_ctu2 (two sub-blocks per lane), under PROF
-  // affine_me_ctu_prof
-  auto big = [&](const KParams& kp) -> int {
-    KParams kb = kp;
-    kb.items = c->dBig1;
-    kb.nItems = c->nBig1;
-    kb.bestS = c->bestS + c->bestOff[0];
-    const unsigned grid = block_grid(c, 1, kb);
-    hipEvent_t t0, t1;
-    if (c->prof) {
-      VAME_TRY(events(1, t0, t1));
-      VAME_HIP(launch_kernel(kernel_for<kKindCtu>(mode), grid, Cfg<kKindCtu>::THREADS, stream, t0, t1,
-                             order_flag(), kb, capture));
-    } else {
-      VAME_TRY(events(3, t0, t1));
-      VAME_HIP(launch_kernel(kernel_for<kKindCtu2>(mode), grid, Cfg<kKindCtu2>::THREADS, stream, t0, t1,
-                             order_flag(), kb, capture));
+  int rc = VAME_OK;
+  int issued = 0;  // VAME_STREAMS=1: kernels after a call's first may start before it ends
+  for (size_t k = 0; k < kps.size() && rc == VAME_OK; k++)
+    for (int i = 0; i < n && rc == VAME_OK; i++) {
+      const int flags = c->streams == 1 && issued++ > 0 ? hipExtAnyOrderLaunch : 0;
+      rc = dispatch(c, plan[i], kps[k], fork && plan[i].side ? c->side : stream, flags, capture);
     }
-    return VAME_OK;
-  };
-  // then the 128x64 and 64x128 CUs: affine_me_half2w / _half2h, under PROF
-  // affine_me_half_prof
-  auto half = [&](const KParams& kp) -> int {
-    if (c->prof) {
-      KParams kh = kp;
-      kh.items = c->dHalf;
-      kh.nItems = c->nHalf;
-      const unsigned grid = block_grid(c, 1, kh);
-      hipEvent_t t0, t1;
-      VAME_TRY(events(2, t0, t1));
-      VAME_HIP(launch_kernel(kernel_for<kKindHalf>(mode), grid, Cfg<kKindHalf>::THREADS, stream, t0, t1,
-                             order_flag(), kh, capture));
-      return VAME_OK;
-    }
-    if (half_merged(mode)) {  // one launch over both orientations: dHalfW then dHalfH, adjacent
-      KParams kh = kp;
-      kh.items = c->dHalfW;
-      kh.nItems = c->nHalfW + c->nHalfH;
-      kh.bestS = c->bestS + c->bestOff[1];  // [pair, CTU, item of 4]: the two regions' span
-      const unsigned grid = block_grid(c, 1, kh);
-      hipEvent_t t0, t1;
-      VAME_TRY(events(4, t0, t1));
-      VAME_HIP(launch_kernel(kernel_for<kKindHalf2W + 100>(mode), grid, Cfg<kKindHalf2W>::THREADS, stream, t0,
-                             t1, order_flag(), kh, capture));
-      return VAME_OK;
-    }
-    for (int o = 0; o < 2; o++) {
-      KParams kh = kp;
-      kh.items = o ? c->dHalfH : c->dHalfW;
-      kh.nItems = o ? c->nHalfH : c->nHalfW;
-      kh.bestS = c->bestS + c->bestOff[1 + o];
-      const unsigned grid = block_grid(c, 1, kh);
-      hipEvent_t t0, t1;
-      VAME_TRY(events(4 + o, t0, t1));
-      VAME_HIP(launch_kernel(o ? kernel_for<kKindHalf2H>(mode) : kernel_for<kKindHalf2W>(mode), grid,
-                             Cfg<kKindHalf2W>::THREADS, stream, t0, t1, order_flag(), kh, capture));
-    }
-    return VAME_OK;
-  };
-  // the quadrant items: set 0 (affine_me_quad), 1 (affine_me_quad2) or, under
-  // PROF, 2 (every quadrant CU in affine_me_quad_prof)
-  const int aset = quadFull && quadHalf ? 2 : quadFull ? 0 : 1;
-  auto quad = [&](const KParams& kp, int set, hipStream_t s) -> int {
-    KParams kq = kp;
-    kq.items = c->dQuad + c->quadOff[set][aset];
-    kq.nItems = c->quadN[set][aset];
-    kq.bestS = c->bestS + c->bestOff[3];
-    const unsigned grid = block_grid(c, 0, kq);
-    hipEvent_t t0, t1;
-    VAME_TRY(events(set == 1 ? 6 : 0, t0, t1));
-    if (set == 1)
-      VAME_HIP(launch_kernel(kernel_for<kKindQuad2>(mode), grid, Cfg<kKindQuad2>::THREADS, s, t0, t1, order_flag(),
-                             kq, capture));
-    else
-      VAME_HIP(launch_kernel(quad_kernel(c->prof, mode), grid, Cfg<kKindQuad>::THREADS, s, t0, t1, order_flag(),
-                             kq, capture));
-    return VAME_OK;
-  };
-  const bool anyQuad = quadFull || quadHalf;
-  // the split packing: affine_me_quad2 on the quadrant stream, affine_me_quad
-  // after the 128-class kernels on the caller's stream (one stream: both
-  // quadrant kernels first)
-  const bool kSplit = VAME_SPLIT == 1 || (VAME_SPLIT == 3 && mode != 1);  // the SBL2 items apart
-  auto quads = [&](const KParams& kp, hipStream_t s1) -> int {
-    if (c->prof || VAME_SPLIT == 0) return quad(kp, 2, sQuad);
-    if (!kSplit) return quad(kp, 3, sQuad);
-    VAME_TRY(quad(kp, 1, sQuad));
-    if (s1 == sQuad || !fork) VAME_TRY(quad(kp, 0, s1));
-    return VAME_OK;
-  };
-  auto all = [&]() -> int {
-    for (const KParams& kp : kps) {
-      if (!fork && anyQuad) VAME_TRY(quads(kp, stream));  // one stream: the quadrant kernels first
-      if (bigItems) {
-        VAME_TRY(big(kp));
-        VAME_TRY(half(kp));
-      }
-      if (fork) {
-        VAME_TRY(quads(kp, kQ1Side ? sQuad : stream));
-        if (!kQ1Side && !c->prof && kSplit) VAME_TRY(quad(kp, 0, c->side2 ? c->side2 : stream));
-      }
-    }
-    return fork ? join() : VAME_OK;
-  };
-  const int rc = all();
-  if (rc != VAME_OK && fork) {
-    // a launch failed after earlier kernels went to the side stream: order
-    // them before the caller's stream anyway, so the caller never frees or
-    // reuses result buffers they still write (best effort, the first error is
-    // the one reported)
-    (void)join();
+  // after a failed launch too: earlier kernels went to the side stream, so
+  // order them before the caller's stream anyway -- the caller never frees or
+  // reuses result buffers they still write (best effort, the first error is
+  // the one reported)
+  if (fork) {
+    const int jrc = join_side(c, stream, capture);
+    if (rc == VAME_OK) rc = jrc;
   }
   return rc;
 }
@@ -909,10 +838,7 @@ int vame_create(vame_ctx** out, int device, int width, int height) {
   // caller's own copy streams on the quadrant kernel's queue (the CLI's
   // compute, upload and download streams + the side stream are four)
   if (e == hipSuccess && c->streams == 2) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
-  if (e == hipSuccess && c->streams == 2 && VAME_SPLIT != 2 && VAME_Q1_SIDE == 2)
-    e = hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->evJoin2, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->bestEv, hipEventDisableTiming);
   if (e == hipSuccess && c->valueSync) {
@@ -997,8 +923,7 @@ void vame_destroy(vame_ctx* c) {
   for (int k = 0; k < 2; k++)
     if (c->dOrder[k]) (void)hipFree(c->dOrder[k]);
   if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->side2) (void)hipStreamDestroy(c->side2);
-  for (hipEvent_t e : {c->evJoin, c->evJoin2, c->evFork, c->bestEv, c->packEv})
+  for (hipEvent_t e : {c->evJoin, c->evFork, c->bestEv, c->packEv})
     if (e) (void)hipEventDestroy(e);
   if (c->syncWord) (void)hipFree(c->syncWord);
   if (c->dPackSegs) (void)hipFree(c->dPackSegs);
@@ -1064,23 +989,28 @@ static bool set_result(const int64_t* (&cost)[4][4], const int32_t* (&cpmv)[4][4
   return true;
 }
 
-// vame_affine_mc (ncus_dev NULL) and vame_affine_mc_dev (ncus = the capacity)
-static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
-                     const vame_mc_cu* cus, int ncus, const int32_t* ncus_dev, float lambda, uint16_t* pred,
-                     int64_t* cost, int32_t* bad, void* stream) {
+// vame_affine_mc (ncus_dev NULL), vame_affine_mc_dev (ncus = the capacity)
+// and, over bi descriptors (CU = vame_mc_bicu), vame_affine_mc_bi
+extern "C++" {
+template <typename CU>
+static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, const CU* cus,
+                     int ncus, const int32_t* ncus_dev, float lambda, uint16_t* pred, int64_t* cost, int32_t* bad,
+                     void* stream) {
+  constexpr bool bi = std::is_same<CU, vame_mc_bicu>::value;
   if (!c || !refs || nrefs < 1 || nrefs > 4 || ncus < 0 || ncus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
   if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
   // the kernel reads window rows as dwords and moves block rows as 8-byte words
   if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
-  McParams p;
+  typename std::conditional<bi, McBiParams, McParams>::type p;
   memset(&p, 0, sizeof(p));
   if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  if (bi && c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
   if (ncus == 0) return VAME_OK;
   if (!cus) return VAME_E_INVALID;
   DeviceGuard guard(c->device);
   VAME_HIP(guard.err);
   p.cur = cur;
-  p.cus = reinterpret_cast<const McCu*>(cus);
+  p.cus = reinterpret_cast<decltype(p.cus)>(cus);
   p.pred = pred;
   p.cost = cost;
   p.bad = bad;
@@ -1092,9 +1022,14 @@ static int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* re
   p.H = c->H;
   p.lambda = lambda;
   p.ncusDev = ncus_dev;
-  VAME_HIP(mc_launch(p, c->prof, (hipStream_t)stream));
+  if constexpr (bi) {
+    VAME_HIP(mc_bi_launch(p, (hipStream_t)stream));
+  } else {
+    VAME_HIP(mc_launch(p, c->prof, (hipStream_t)stream));
+  }
   return VAME_OK;
 }
+}  // extern "C++"
 
 int vame_affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
                    const vame_mc_cu* cus, int ncus, float lambda, uint16_t* pred, int64_t* cost,
@@ -1109,64 +1044,59 @@ int vame_affine_mc_dev(vame_ctx* c, const uint16_t* cur, const uint16_t* const* 
   return affine_mc(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, pred, cost, bad, stream);
 }
 
-int vame_partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty,
-                   vame_mc_cu* cus, int32_t* rows, int32_t* ncus, int32_t* ctu_info, int64_t* ctu_cost,
-                   int32_t* block_cu, void* stream) {
-  if (!c || !res || nrefs < 1 || nrefs > 4 || !cus || !ncus) return VAME_E_INVALID;
+// vame_partition and (bi: leaves may be bi-predicted, `cus` holds vame_mc_bicu
+// descriptors) vame_partition_bi
+static int partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty, bool bi,
+                     const int64_t* const* bi_cost, const int32_t* const* bi_sel, int64_t bi_penalty, void* cus,
+                     int32_t* rows, int32_t* sel, int32_t* ncus, int32_t* ctu_info, int64_t* ctu_cost,
+                     int32_t* block_cu, void* stream) {
+  if (!c || !res || nrefs < 1 || nrefs > 4 || !cus || !ncus || (bi && (!bi_cost || !bi_sel))) return VAME_E_INVALID;
   if ((pred_mask & ~15) || !(pred_mask & 3)) return VAME_E_INVALID;  // at least one FULL PRED
   if (split_penalty < 0 || split_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
+  if (bi_penalty < 0 || bi_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
   PartParams p;
   memset(&p, 0, sizeof(p));
   if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
+  for (int a = 0; bi && a < 2; a++) {
+    if (!((pred_mask >> (2 * a)) & 3)) continue;
+    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
+    p.biCost[a] = bi_cost[a];
+    p.biSel[a] = bi_sel[a];
+  }
+  if (bi && c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
   DeviceGuard guard(c->device);
   VAME_HIP(guard.err);
   p.cus = reinterpret_cast<McCu*>(cus);
   p.rows = rows;
+  p.sel = sel;
   p.ncus = ncus;
   p.ctuInfo = ctu_info;
   p.ctuCost = ctu_cost;
   p.blockCu = block_cu;
   p.scratch = c->partScratch;
   p.penalty = split_penalty;
+  p.biPenalty = bi_penalty;
   p.nrefs = nrefs;
   p.predMask = pred_mask;
   p.W = c->W;
   p.H = c->H;
   p.nCtus = c->nCtus;
   p.ctusPerRow = c->ctusPerRow;
-  VAME_HIP(partition_launch(p, (hipStream_t)stream));
+  VAME_HIP(partition_launch(p, (hipStream_t)stream, bi));
   return VAME_OK;
+}
+
+int vame_partition(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty,
+                   vame_mc_cu* cus, int32_t* rows, int32_t* ncus, int32_t* ctu_info, int64_t* ctu_cost,
+                   int32_t* block_cu, void* stream) {
+  return partition(c, res, nrefs, pred_mask, split_penalty, false, nullptr, nullptr, 0, cus, rows, nullptr, ncus,
+                   ctu_info, ctu_cost, block_cu, stream);
 }
 
 int vame_affine_mc_bi(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
                       const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
                       uint16_t* pred, int64_t* cost, int32_t* bad, void* stream) {
-  if (!c || !refs || nrefs < 1 || nrefs > 4 || max_cus < 0 || max_cus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
-  if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
-  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(pred)) & 7) return VAME_E_INVALID;
-  McBiParams p;
-  memset(&p, 0, sizeof(p));
-  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
-  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
-  if (max_cus == 0) return VAME_OK;
-  if (!cus) return VAME_E_INVALID;
-  DeviceGuard guard(c->device);
-  VAME_HIP(guard.err);
-  p.cur = cur;
-  p.cus = reinterpret_cast<const McBiCu*>(cus);
-  p.pred = pred;
-  p.cost = cost;
-  p.bad = bad;
-  p.offs = c->mcScratch;
-  p.blockSum = c->mcScratch + kMcMaxCus + 1;
-  p.ncus = max_cus;
-  p.nrefs = nrefs;
-  p.W = c->W;
-  p.H = c->H;
-  p.lambda = lambda;
-  p.ncusDev = ncus_dev;
-  VAME_HIP(mc_bi_launch(p, (hipStream_t)stream));
-  return VAME_OK;
+  return affine_mc(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, pred, cost, bad, stream);
 }
 
 int vame_bipred(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
@@ -1212,40 +1142,8 @@ int vame_partition_bi(vame_ctx* c, const vame_poc_result* res, int nrefs, int pr
                       const int64_t* const bi_cost[2], const int32_t* const bi_sel[2], int64_t bi_penalty,
                       vame_mc_bicu* cus, int32_t* rows, int32_t* sel, int32_t* ncus, int32_t* ctu_info,
                       int64_t* ctu_cost, int32_t* block_cu, void* stream) {
-  if (!c || !res || nrefs < 1 || nrefs > 4 || !cus || !ncus || !bi_cost || !bi_sel) return VAME_E_INVALID;
-  if ((pred_mask & ~15) || !(pred_mask & 3)) return VAME_E_INVALID;  // at least one FULL PRED
-  if (split_penalty < 0 || split_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
-  if (bi_penalty < 0 || bi_penalty > (int64_t(1) << 40)) return VAME_E_INVALID;
-  PartParams p;
-  memset(&p, 0, sizeof(p));
-  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
-  for (int a = 0; a < 2; a++) {
-    if (!((pred_mask >> (2 * a)) & 3)) continue;
-    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
-    p.biCost[a] = bi_cost[a];
-    p.biSel[a] = bi_sel[a];
-  }
-  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
-  DeviceGuard guard(c->device);
-  VAME_HIP(guard.err);
-  p.cus = reinterpret_cast<McCu*>(cus);
-  p.rows = rows;
-  p.sel = sel;
-  p.ncus = ncus;
-  p.ctuInfo = ctu_info;
-  p.ctuCost = ctu_cost;
-  p.blockCu = block_cu;
-  p.scratch = c->partScratch;
-  p.penalty = split_penalty;
-  p.biPenalty = bi_penalty;
-  p.nrefs = nrefs;
-  p.predMask = pred_mask;
-  p.W = c->W;
-  p.H = c->H;
-  p.nCtus = c->nCtus;
-  p.ctusPerRow = c->ctusPerRow;
-  VAME_HIP(partition_launch(p, (hipStream_t)stream, true));
-  return VAME_OK;
+  return partition(c, res, nrefs, pred_mask, split_penalty, true, bi_cost, bi_sel, bi_penalty, cus, rows, sel, ncus,
+                   ctu_info, ctu_cost, block_cu, stream);
 }
 
 int vame_bipred_refine(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,

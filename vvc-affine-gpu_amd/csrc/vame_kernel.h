@@ -1147,9 +1147,6 @@ struct CuState {
 // reduction, solve, update) covers twice the sub-blocks it does in
 // affine_me_quad, which keeps the 16-sub-block CUs and the 64x64 CUs.
 enum { kKindQuad = 0, kKindCtu = 1, kKindHalf = 2, kKindCtu2 = 3, kKindHalf2W = 4, kKindHalf2H = 5, kKindQuad2 = 6 };
-#ifndef VAME_QUAD2_STASH
-#define VAME_QUAD2_STASH 0
-#endif
 template <int KIND>
 struct Cfg {
   static constexpr bool HALF2 = KIND == kKindHalf2W || KIND == kKindHalf2H;
@@ -1173,9 +1170,9 @@ struct Cfg {
   // SBL = 2: the upper sub-block's prediction parked in LDS across the lower
   // one's (held in registers: +3 % time at c4); affine_me_half2* keep it in
   // registers, so that four workgroups fit a CU's LDS (parked in LDS, three
-  // per CU: 8 % slower, HISTORY.md)
-  // (affine_me_quad2: in registers, VAME_QUAD2_STASH=1 parks it in LDS)
-  static constexpr bool STASH = KIND == kKindQuad2 ? VAME_QUAD2_STASH != 0 : !HALF2;
+  // per CU: 8 % slower, HISTORY.md), and so does affine_me_quad2 (parked in
+  // LDS it loses a workgroup per CU: 3 % slower at c2, 5 % at c4, HISTORY.md)
+  static constexpr bool STASH = KIND != kKindQuad2 && !HALF2;
 };
 
 // Value i of a sub-block's contribution to its CU's normal equations
@@ -2269,16 +2266,13 @@ __device__ __forceinline__ bool quad_item_sbl2(const KParams& p) {
   return (p.items[gr / p.groupPer].coop & 4) != 0;
 }
 //
-// Which launch modes hand affine_me_quad SBL2 items (engine, VAME_SPLIT): by
-// default only the 2-CP-only launches; in the others the SBL2 items go to
+// Which launch modes hand affine_me_quad SBL2 items (the engine's launch
+// plan): only the 2-CP-only launches; in the others the SBL2 items go to
 // affine_me_quad2 and affine_me_quad is built without the two-sub-block body,
 // whose registers would otherwise spill into the one-sub-block body too
-// (104 vs 0 B per lane in MODE 3).  Timing builds: 2 every mode, 1 / 0 none.
-#ifndef VAME_SPLIT
-#define VAME_SPLIT 3
-#endif
+// (104 vs 0 B per lane in MODE 3).
 template <int MODE>
-constexpr bool kQuadMerged = VAME_SPLIT == 2 || (VAME_SPLIT == 3 && MODE == 1);
+constexpr bool kQuadMerged = MODE == 1;
 template <int MODE>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void affine_me_quad(
     KParams p) {
@@ -2291,7 +2285,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
   }
   affine_me_body<kKindQuad, false, MODE>(p, lds);
 }
-// Timing builds (VAME_SPLIT=1): the SBL2 items as a kernel of their own.
+// The SBL2 items as a kernel of their own (MODE 2 and 3).
 template <int MODE>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void affine_me_quad2(
     KParams p) {
@@ -2320,7 +2314,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void a
 }
 // Both orientations in one launch (an item's region width tells which), so
 // the 128x64 and 64x128 CUs run side by side instead of one kernel after the
-// other on the stream; the 64x128 layout's LDS holds the 128x64 one's.
+// other on the stream; the 64x128 layout's LDS holds the 128x64 one's.  MODE
+// 1 only: with 3-CP the two bodies in one kernel spill (88 vs 20 B per lane).
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void affine_me_half2(KParams p) {
   __shared__ Lds<kKindHalf2H, MODE == 3> lds;
@@ -2355,8 +2350,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
 // The 2-CP-only (MODE 1) product kernels are compiled in a translation unit of
 // their own, vame_kernels_2cp.hip, whose optimisation flags suit them (the
 // Makefile); the engine's unit declares them instead of
-// instantiating them.  Instrumentation builds keep every kernel in one unit:
-// their device counters are per unit.
+// instantiating them.  They are the MODE 1 kernels the engine launches: the
+// split kernels (affine_me_quad2, affine_me_half2w / _half2h) have no MODE 1
+// instance.  Instrumentation builds keep every kernel in one unit: their
+// device counters are per unit.
 #if VAME_COUNT_PRED || VAME_PHASE_TIMING
 #define VAME_SPLIT_TU 0
 #else
@@ -2364,11 +2361,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
 #endif
 #define VAME_2CP_KERNELS(X)                 \
   X template __global__ void affine_me_quad<1>(KParams);   \
-  X template __global__ void affine_me_quad2<1>(KParams);  \
   X template __global__ void affine_me_ctu2<1>(KParams);   \
-  X template __global__ void affine_me_half2<1>(KParams);  \
-  X template __global__ void affine_me_half2w<1>(KParams); \
-  X template __global__ void affine_me_half2h<1>(KParams);
+  X template __global__ void affine_me_half2<1>(KParams);
 
 // ------------------------------------------- partition decision (vame_partition.hip)
 struct McCu;                      // the descriptor it emits (vame_mc_core.h)

@@ -81,9 +81,12 @@ class Engine:
 
     def get_timing(self, kernel_class: int, reset: bool = True):
         """(total_ms, launches) of kernel class 0 (quadrant items, affine_me_quad) /
+        6 (those of 32 to 128 sub-blocks in launches with 3-CP, affine_me_quad2) /
         3 (128x128 CUs, affine_me_ctu2) / 4, 5 (128x64 / 64x128 CUs,
-        affine_me_half2w / affine_me_half2h); under PROF 1 (128x128 CUs,
-        affine_me_ctu_prof) / 2 (128x64 and 64x128 CUs, affine_me_half_prof)."""
+        affine_me_half2w / affine_me_half2h; in 2-CP-only launches 4 is both, in
+        one affine_me_half2 launch); under PROF 0 (affine_me_quad_prof) / 1
+        (128x128 CUs, affine_me_ctu_prof) / 2 (128x64 and 64x128 CUs,
+        affine_me_half_prof)."""
         t, n = ctypes.c_double(), ctypes.c_int()
         check(lib().vame_get_timing(self._h, kernel_class, ctypes.byref(t), ctypes.byref(n), int(reset)))
         return t.value, n.value

@@ -324,6 +324,79 @@ int vame_bipred_refine(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const
                        const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
                        int rounds, vame_mc_bicu* out, int64_t* cost, int32_t* bad, void* stream);
 
+/* ---- Seeding the affine search.  The search starts every
+ * 2-CP candidate at zero CPMVs and follows motion of a few samples; these
+ * calls give it the translational start an encoder has.  All three read
+ * nothing on the host, allocate and synchronize nothing, run on `stream` alone
+ * (never the side stream) and can be captured; every output entry is written
+ * by the call's kernels; all sums are integer or run in solveEqual's fixed
+ * order: identical from run to run. */
+
+/* The best integer displacement of every candidate CU.  For every r < nrefs,
+ * every alignment in align_mask (bit 0 FULL, bit 1 HALF) and every row
+ * ctu*{201|284} + offset, whose CU is (x, y, w, h) at frame position:
+ *   CU not wholly in the frame: mv = (0, 0), cost = INT64_MAX.
+ *   candidates  integer d = (dx, dy), |dx|, |dy| <= radius, dx <= W+7-x and
+ *               dy <= H+7-y: the displacements whose MV (16dx, 16dy) clipMv
+ *               leaves unchanged at the CU's position
+ *   value       SAD(d) + floor(lambda * (bits + 2)): SAD(d) = sum |cur[y+j][x+i]
+ *               - ref[clamp(y+dy+j, 0, H-1)][clamp(x+dx+i, 0, W-1)]|, bits = the
+ *               search's bits of the 2-CP CPMVs LT = RT = (16dx, 16dy) -- the
+ *               block is vame_affine_mc's prediction of those CPMVs, the rate
+ *               the search's rate of them
+ *   selection   mv = (16dx, 16dy) of the first minimum under strict <, in the
+ *               order (0, 0), then dy = -radius..radius (outer), dx =
+ *               -radius..radius (inner); cost = that value
+ * radius 0..32 (0: mv 0 and the value of (0, 0)).  mv / cost of (r, alignment):
+ * nCtus*{201|284} entries (device); entries outside the mask may be NULL and
+ * are not touched.  PROF does not enter.  Argument errors (nrefs outside 1..4,
+ * an empty or unknown mask, a radius outside 0..32, a NULL output of an
+ * (r, alignment) in the mask, a misaligned frame: cur 8 bytes, refs 4):
+ * VAME_E_INVALID, nothing written. */
+typedef struct { vame_mv* mv[4][2]; int64_t* cost[4][2]; } vame_seed_result;   /* [ref][align] */
+int vame_seed_search(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                     float lambda, int align_mask, int radius, const vame_seed_result* out, void* stream);
+
+/* The search's iteration from caller-given CPMVs, on a CU list: the first
+ * min(*ncus_dev, max_cus) descriptors (ncus_dev NULL: max_cus; a negative
+ * count is 0); entries at or past the count are neither read nor written.
+ * A valid descriptor (vame_affine_mc's rules): oracle/vame_oracle.c:run_cu
+ * with init = its CPMVs, nCP = its nCPs, niter = (5 | 4) + extra_grad_iter,
+ * PROF off; out[i] is the descriptor with the best CPMVs and cost[i] its cost,
+ * bit for bit vame_affine_mc's cost of out[i].  Iteration 0's cost always
+ * becomes the best; a 2-CP descriptor keeps its LB as given.  An invalid
+ * descriptor is copied through, costs 0 and ORs 1 into *bad.  out may be cus.
+ * It uses no scratch of the context.  extra_grad_iter 0..64.  While
+ * vame_set_prof(ctx, 1) is in force: VAME_E_UNSUPPORTED, nothing written.
+ * Argument errors as vame_bipred_refine's. */
+int vame_affine_search(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_cu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                       int extra_grad_iter, vame_mc_cu* out, int64_t* cost, int32_t* bad, void* stream);
+
+/* Improve a POC's search results in place from seeds.  res holds the results
+ * of vame_affine_me_poc for the same cur / refs / lambda / mode_mask / extra.
+ * For every r, every alignment a in the mask and every row whose CU is wholly
+ * in the frame and whose seed seed_mv[r][a][row] is not (0, 0):
+ *   d2 = vame_affine_search's rule with nCPs = 2, LT = RT = seed, LB = 0;
+ *   with 3-CP in the mask, d3 = that rule with nCPs = 3 from d2's best CPMVs
+ *   and the LB the fused search derives from them (affine.cl:81-105);
+ *   res[r][2a] takes d2's row where d2.cost < its cost, res[r][2a+1] d3's row
+ *   where d3.cost < its cost: cost and CPMVs together, nCPs as the search
+ *   writes it.
+ * Every other row is untouched; with all seeds zero the call changes nothing.
+ * Seeds need not come from vame_seed_search: any MV with components in
+ * [-2^17, 2^17-1] is a start; a seed outside that range skips its row and ORs
+ * 1 into *bad.  mode_mask as the fused calls take it (2-CP required).  work:
+ * caller memory (device, 8-byte aligned) of at least vame_seeded_work_bytes
+ * (0 for bad arguments): the descriptor lists and device counts the call
+ * builds.  While PROF is on: VAME_E_UNSUPPORTED.  Argument errors:
+ * VAME_E_INVALID, nothing written. */
+size_t vame_seeded_work_bytes(vame_ctx* ctx, int nrefs, int mode_mask);
+int vame_affine_me_seeded(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                          float lambda, int mode_mask, int extra_grad_iter,
+                          vame_mv* const seed_mv[4][2], const vame_poc_result* res /* in-out */,
+                          void* work, size_t work_bytes, int32_t* bad, void* stream);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

@@ -13,7 +13,8 @@
 // (2 / 8 / 32 KB) for the Sobel neighbourhood, the 24 int64 moments and the
 // 6x7 FP64 system.  Every step of the iteration is the search's device
 // function (vame_kernel.h): mv_field, filter_rows_global, satd_4x4, grad_sb,
-// eq_value, seg_solve, scale_delta; only the loop around them is new.
+// eq_value, seg_solve, scale_delta; the gradient step and the workgroup sums
+// are vame_refine_core.h's, shared with vame_search.hip.
 //
 // Operand widths with |e| <= 2046 (the search has |e| <= 1023): e and
 // 2 cur - P_fixed (-1023 .. 2046) fit the packed int16 lanes of grad_sb; its
@@ -23,51 +24,9 @@
 #include <hip/hip_runtime.h>
 
 #include "vame_birefine.h"
+#include "vame_refine_core.h"
 
 namespace vame {
-
-static_assert(kNumVal2 <= kNumMom, "one moment table for both models");
-
-__device__ __forceinline__ int br_wave_sum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ long long br_wave_sum64(long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// Sum of `v` over the workgroup, in every lane (called by all of them).
-template <int NT>
-__device__ __forceinline__ long long br_block_sum(int v, unsigned long long* s_sum) {
-  v = br_wave_sum(v);
-  if constexpr (NT == 64) return v;
-  __syncthreads();  // the readers of the previous sum are done
-  if (threadIdx.x == 0) *s_sum = 0;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) atomicAdd(s_sum, (unsigned long long)(long long)v);
-  __syncthreads();
-  return (long long)*s_sum;
-}
-
-// The lane's share of the CU's moments (eq_value's order) into s_V: the sum
-// over its sub-blocks, a wave sum, then one 64-bit LDS add per wave and value
-// (integer: any order).
-template <int NCP, int SB>
-__device__ __forceinline__ void br_accumulate(const int (&S)[SB][5], int u, const int (&v)[SB], long long* s_V) {
-  constexpr int NV = NCP == 3 ? kNumMom : kNumVal2;
-#pragma unroll
-  for (int k = 0; k < NV; k++) {
-    long long t = 0;
-#pragma unroll
-    for (int q = 0; q < SB; q++) t += eq_value<NCP>(k, S[q], u, v[q]);
-    t = br_wave_sum64(t);
-    if ((threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(s_V + k), (unsigned long long)t);
-    __builtin_amdgcn_sched_barrier(0);  // one value at a time, not 24 of them in flight
-  }
-}
 
 // NT lanes, SB sub-blocks per lane: sub-block tid + q * NT, q < SB, so a lane's
 // sub-blocks share their column (NT is a multiple of the CU's sub-block row).
@@ -224,56 +183,7 @@ __global__ __launch_bounds__(NT) void birefine_kernel(BiRefineParams p) {
       if (it == niter) break;
 
       // one step of the search's update on P_m with e = 2 cur - P_f - P_m
-      if (tid < kNumMom) s_V[tid] = 0;
-      __syncthreads();
-      int S[SB][5] = {};
-      int vq[SB];
-#pragma unroll
-      for (int q = 0; q < SB; q++) vq[q] = sy + q * syStep + 2;
-      if (active) {
-        const uint16_t* pm16 = reinterpret_cast<const uint16_t*>(s_pm);
-        const int xl = max(sx - 1, 0), xr = min(sx + 4, cu.w - 1);
-#pragma unroll
-        for (int q = 0; q < SB; q++) {
-          if (q >= nq) break;
-          const int syq = sy + q * syStep;
-          uint4 X[6];
-#pragma unroll
-          for (int k = 0; k < 6; k++) {
-            const int row = clampi(syq - 1 + k, 0, cu.h - 1) * cu.w;
-            const uint2 pq = s_pm[(row + sx) >> 2];
-            X[k] = ext_row(pq, (unsigned)pm16[row + xl] << 16, (unsigned)pm16[row + xr]);
-          }
-          grad_sb(sx, syq, g, X, Of[q], S[q]);
-        }
-      }
-      if (nM == 3)
-        br_accumulate<3, SB>(S, sx + 2, vq, s_V);
-      else
-        br_accumulate<2, SB>(S, sx + 2, vq, s_V);
-      __syncthreads();
-      if (tid < 64) {  // the first wave solves; the deltas come back in s_M[0 .. 2 nM)
-        double dd[6];
-        if (nM == 3)
-          seg_solve<3, true>(s_V, s_M, kEqMap.v, tid, 64, true, false, lw, lh, dd);
-        else
-          seg_solve<2, true>(s_V, s_M, kEqMap.v, tid, 64, true, false, lw, lh, dd);
-      }
-      __syncthreads();
-      bool moved = false;
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        if (j < 2 * nM) {  // a 2-CP hypothesis never changes LB
-          const double d = s_M[j == 1 ? 2 : j == 2 ? 1 : j];  // LT = (d0, d2), RT = (d1, d3), LB = (d4, d5)
-          int v = (int)((unsigned)cc[j] + (unsigned)scale_delta(d));
-          v = clampi(v, kMvMin, kMvMax);
-          const int pos = (j & 1) ? cu.y : cu.x, lim = (j & 1) ? H : W;
-          v = clampi(v, shl(-128 - 8 - pos + 1, 4), shl(lim + 8 - pos - 1, 4));  // clipMv
-          moved = moved || v != cc[j];
-          cc[j] = v;
-        }
-      }
-      __syncthreads();  // s_M, s_V and s_pm are free again
+      const bool moved = br_step<NT, SB>(s_pm, Of, s_V, s_M, g, nM, active, nq, sx, sy, syStep, W, H, cc);
       // unchanged CPMVs repeat this iteration's prediction and cost: never strictly better
       if (!moved) break;
     }

@@ -19,6 +19,8 @@
 #include "vame_mc_core.h"
 #include "vame_bipred.h"
 #include "vame_birefine.h"
+#include "vame_search.h"
+#include "vame_seed.h"
 
 #if VAME_SPLIT_TU
 namespace vame {
@@ -1174,6 +1176,122 @@ int vame_bipred_refine(vame_ctx* c, const uint16_t* cur, const uint16_t* const* 
   p.lambda = lambda;
   p.ncusDev = ncus_dev;
   VAME_HIP(birefine_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_seed_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                     int align_mask, int radius, const vame_seed_result* out, void* stream) {
+  if (!c || !cur || !refs || !out || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if ((align_mask & ~3) || !align_mask || radius < 0 || radius > kSeedMaxRadius) return VAME_E_INVALID;
+  // the kernel reads block rows of cur as 8-byte words and reference rows as dwords
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  SeedParams p;
+  memset(&p, 0, sizeof(p));
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  for (int r = 0; r < nrefs; r++)
+    for (int a = 0; a < 2; a++) {
+      if (!((align_mask >> a) & 1)) continue;
+      if (!out->mv[r][a] || !out->cost[r][a]) return VAME_E_INVALID;
+      p.cost[r][a] = out->cost[r][a];
+      p.mv[r][a] = reinterpret_cast<int32_t*>(out->mv[r][a]);
+    }
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.nCtus = c->nCtus;
+  p.ctusPerRow = c->ctusPerRow;
+  p.radius = radius;
+  p.lambda = lambda;
+  VAME_HIP(seed_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_affine_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       const vame_mc_cu* cus, int max_cus, const int32_t* ncus_dev, float lambda,
+                       int extra_grad_iter, vame_mc_cu* out, int64_t* cost, int32_t* bad, void* stream) {
+  if (!c || !cur || !refs || !cus || !out || !cost || !bad) return VAME_E_INVALID;
+  if (nrefs < 1 || nrefs > 4 || extra_grad_iter < 0 || extra_grad_iter > 64 || max_cus < 0 ||
+      max_cus > VAME_MC_MAX_CUS)
+    return VAME_E_INVALID;
+  // the kernel reads window rows as dwords and block rows as 8-byte words
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  SearchParams p;
+  memset(&p, 0, sizeof(p));
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  if (c->prof) return VAME_E_UNSUPPORTED;  // no PROF form
+  if (max_cus == 0) return VAME_OK;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cus = reinterpret_cast<const McCu*>(cus);
+  p.out = reinterpret_cast<McCu*>(out);
+  p.cost = cost;
+  p.bad = bad;
+  p.maxCus = max_cus;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.extra = extra_grad_iter;
+  p.lambda = lambda;
+  p.ncusDev = ncus_dev;
+  VAME_HIP(search_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+// The in-frame candidates of the alignments a valid mode mask codes: their
+// range in the context's table.
+static bool seeded_range(vame_ctx* c, int mode_mask, int& begin, int& end) {
+  if (!(mode_mask & VAME_MODE_2CP) || (mode_mask & ~15)) return false;
+  const int preds = vame_pred_mask(mode_mask);
+  begin = (preds & 3) ? 0 : c->biNCand[0];
+  end = (preds & 12) ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
+  return true;
+}
+
+size_t vame_seeded_work_bytes(vame_ctx* c, int nrefs, int mode_mask) {
+  int begin, end;
+  if (!c || nrefs < 1 || nrefs > 4 || !seeded_range(c, mode_mask, begin, end)) return 0;
+  return seeded_work_bytes((size_t)nrefs * (end - begin), (mode_mask & VAME_MODE_3CP) != 0);
+}
+
+int vame_affine_me_seeded(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                          int mode_mask, int extra_grad_iter, vame_mv* const seed_mv[4][2],
+                          const vame_poc_result* res, void* work, size_t work_bytes, int32_t* bad, void* stream) {
+  if (!c || !cur || !refs || !seed_mv || !res || !work || !bad || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if (extra_grad_iter < 0 || extra_grad_iter > 64) return VAME_E_INVALID;
+  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(work)) & 7) return VAME_E_INVALID;
+  SeededParams p;
+  memset(&p, 0, sizeof(p));
+  if (!seeded_range(c, mode_mask, p.candBegin, p.candEnd)) return VAME_E_INVALID;
+  const int preds = vame_pred_mask(mode_mask);
+  if (!set_refs(p.search.refs, refs, nrefs)) return VAME_E_INVALID;
+  for (int r = 0; r < nrefs; r++)
+    for (int m = 0; m < 4; m++) {
+      if (!((preds >> m) & 1)) continue;
+      if (!res->cost[r][m] || !res->cpmvs[r][m] || !seed_mv[r][m >> 1]) return VAME_E_INVALID;
+      p.cost[r][m] = res->cost[r][m];
+      p.cpmv[r][m] = reinterpret_cast<int32_t*>(res->cpmvs[r][m]);
+      p.seed[r][m >> 1] = reinterpret_cast<const int32_t*>(seed_mv[r][m >> 1]);
+    }
+  p.with3 = (mode_mask & VAME_MODE_3CP) != 0;
+  p.cap = nrefs * (p.candEnd - p.candBegin);
+  if (work_bytes < seeded_work_bytes((size_t)p.cap, p.with3)) return VAME_E_INVALID;
+  if (c->prof) return VAME_E_UNSUPPORTED;  // no PROF form
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cands = c->biCands;
+  p.work = seeded_work(work, (size_t)p.cap, p.with3);
+  p.search.cur = cur;
+  p.search.bad = bad;
+  p.search.nrefs = nrefs;
+  p.search.W = c->W;
+  p.search.H = c->H;
+  p.search.extra = extra_grad_iter;
+  p.search.lambda = lambda;
+  VAME_HIP(seeded_launch(p, (hipStream_t)stream));
   return VAME_OK;
 }
 

@@ -21,7 +21,8 @@ EXPORTS = (
     "vame_log_writer_sizes", "vame_log_writer_flush_at", "vame_template_coverage", "vame_pack_records",
     "vame_count_lines_ranges", "vame_set_max_pairs", "vame_get_max_pairs", "vame_affine_mc",
     "vame_affine_mc_dev", "vame_partition", "vame_partition_table", "vame_affine_mc_bi", "vame_bipred",
-    "vame_partition_bi", "vame_bipred_refine",
+    "vame_partition_bi", "vame_bipred_refine", "vame_seed_search", "vame_affine_search",
+    "vame_seeded_work_bytes", "vame_affine_me_seeded",
 )
 
 
@@ -31,6 +32,11 @@ class VameError(RuntimeError):
 
 class PocResult(ctypes.Structure):
     _fields_ = [("cost", (ctypes.c_void_p * 4) * 4), ("cpmvs", (ctypes.c_void_p * 4) * 4)]
+
+
+class SeedResult(ctypes.Structure):
+    """vame_seed_result (include/vame.h): [refIdx][align]."""
+    _fields_ = [("mv", (ctypes.c_void_p * 2) * 4), ("cost", (ctypes.c_void_p * 2) * 4)]
 
 
 class PocJob(ctypes.Structure):
@@ -65,6 +71,12 @@ def lib():
         L.vame_partition_bi.argtypes = [P, ctypes.POINTER(PocResult), I, I, ctypes.c_int64, P, P, ctypes.c_int64,
                                         P, P, P, P, P, P, P, P]
         L.vame_bipred_refine.argtypes = [P, P, P, I, P, I, P, F, I, P, P, P, P]
+        L.vame_seed_search.argtypes = [P, P, P, I, F, I, I, ctypes.POINTER(SeedResult), P]
+        L.vame_affine_search.argtypes = [P, P, P, I, P, I, P, F, I, P, P, P, P]
+        L.vame_seeded_work_bytes.argtypes = [P, I, I]
+        L.vame_seeded_work_bytes.restype = ctypes.c_size_t
+        L.vame_affine_me_seeded.argtypes = [P, P, P, I, F, I, I, P, ctypes.POINTER(PocResult), P, ctypes.c_size_t,
+                                            P, P]
         L.vame_num_ctus.argtypes = [I, I]
         L.vame_cus_per_ctu.argtypes = [I]
         L.vame_num_groups.argtypes = [I]

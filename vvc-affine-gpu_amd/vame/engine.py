@@ -16,7 +16,7 @@ import ctypes
 
 import torch
 
-from ._lib import PocJob, PocResult, check, lib
+from ._lib import PocJob, PocResult, SeedResult, check, lib
 
 CPMV_FIELDS = ("nCPs", "LTx", "LTy", "RTx", "RTy", "LBx", "LBy")
 MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
@@ -522,6 +522,114 @@ class Engine:
                 cost[rows] = c
             out["cost"][a], out["sel"][a], out["cus"][a], out["rows"][a] = cost, sel, cus, rows.to(torch.int32)
         return out
+
+    # ---- seeding the search
+    def _check_seed(self, t, a: int, what: str, dtype, tail: tuple):
+        n = self.n_cus(a)
+        if (t is None or t.dtype != dtype or tuple(t.shape) != (n,) + tail or t.device != self.device
+                or not t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} {(n,) + tail} tensor on {self.device}")
+        return t
+
+    def seed_search(self, cur, refs, lam: float, radius: int = 16, aligns: int = 3, out: dict | None = None):
+        """vame_seed_search: the best integer displacement of every candidate
+        CU inside +-radius (0..32) under SAD + the search's rate, first minimum
+        in the order (0, 0), then dy outer, dx inner.  aligns: bit 0 FULL, bit
+        1 HALF.  Returns {"mv": {(r, a): int32 [n, 2]}, "cost": {(r, a): int64
+        [n]}} over the rows of each alignment: mv in 1/16 pel (a start for
+        affine_me_seeded), cost its SAD + rate; rows of CUs that leave the
+        frame hold (0, 0) and INT64_MAX.  out: a dict of an earlier call to
+        write into.  Reads nothing on the host; asynchronous on the current
+        stream."""
+        cur = self._frame(cur)
+        refs, ref_ptrs = self._refs(refs, "seed_search")
+        if not 0 <= int(radius) <= 32:
+            raise ValueError("radius must be in 0..32")
+        if int(aligns) & ~3 or not int(aligns):
+            raise ValueError("aligns must hold bit 0 (FULL), bit 1 (HALF) or both")
+        keys = [(r, a) for r in range(len(refs)) for a in (0, 1) if (aligns >> a) & 1]
+        if out is None:
+            out = {"mv": {k: torch.empty((self.n_cus(k[1]), 2), dtype=torch.int32, device=self.device) for k in keys},
+                   "cost": {k: torch.empty(self.n_cus(k[1]), dtype=torch.int64, device=self.device) for k in keys}}
+        sr = SeedResult()
+        for r, a in keys:
+            try:
+                mv, cost = out["mv"][(r, a)], out["cost"][(r, a)]
+            except (KeyError, TypeError):
+                raise ValueError(f"out['mv'] / out['cost'] miss {(r, a)}") from None
+            sr.mv[r][a] = self._check_seed(mv, a, f"out['mv'][{(r, a)}]", torch.int32, (2,)).data_ptr()
+            sr.cost[r][a] = self._check_seed(cost, a, f"out['cost'][{(r, a)}]", torch.int64, ()).data_ptr()
+        check(lib().vame_seed_search(self._h, _ptr(cur), ref_ptrs, len(refs), float(lam), int(aligns), int(radius),
+                                     ctypes.byref(sr), self._stream()))
+        return out
+
+    def affine_search(self, cus: torch.Tensor, refs, cur, lam: float, extra: int = 0,
+                      ncus: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                      cost: torch.Tensor | None = None):
+        """vame_affine_search: the search's iteration (5 gradient steps for a
+        2-CP, 4 for a 3-CP descriptor, + extra) started at the CPMVs of every
+        descriptor of cus (int32 [n, 12], vame.mc.CU_FIELDS).  Returns (out,
+        cost, bad): the descriptors with the best CPMVs met, int64 [n] their
+        costs -- exactly affine_mc's costs of `out` -- and the int32 flag of an
+        invalid descriptor (copied through, cost 0).  ncus: an int32 scalar on
+        the device, the number of descriptors to work on (entries past it stay
+        untouched); out may be cus.  Reads nothing on the host; asynchronous on
+        the current stream.  Not available under PROF."""
+        self._check_cus(cus, 12)
+        if not 0 <= int(extra) <= 64:
+            raise ValueError("extra must be in 0..64")
+        refs, ref_ptrs = self._refs(refs, "affine_search")
+        cur = self._frame(cur)
+        n = cus.shape[0]
+        self._check_scalar(ncus, "ncus")
+        if out is None:
+            out = torch.empty_like(cus)
+        else:
+            self._check_cus(out, 12, "out", n)
+        if cost is None:
+            cost = torch.empty(n, dtype=torch.int64, device=self.device)
+        elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
+              or not cost.is_contiguous()):
+            raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_affine_search(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(ncus), float(lam),
+                                       int(extra), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
+        return out, cost, bad
+
+    def affine_me_seeded(self, cur, refs, lam: float, result: dict, seeds: dict, modes: int = 3, extra: int = 0):
+        """vame_affine_me_seeded: improve `result` (the alloc_poc dict
+        affine_me_poc filled for the same cur, refs, lam, modes and extra) in
+        place: every row with a non-zero seed runs the 2-CP search from LT =
+        RT = seed and, with 3-CP in modes, the 3-CP search from that winner;
+        a row takes the new cost and CPMVs where the cost is strictly lower.
+        seeds: {(r, a): int32 [n, 2]} (seed_search()["mv"], or any MVs with
+        components in [-2^17, 2^17 - 1]).  Returns (result, bad): bad is 1 when
+        a seed was out of range (its row is skipped).  torch allocates the work
+        buffer.  Reads nothing on the host; asynchronous on the current stream.
+        Not available under PROF."""
+        cur = self._frame(cur)
+        refs, ref_ptrs = self._refs(refs, "affine_me_seeded")
+        if not int(modes) & MODE_2CP or int(modes) & ~15:
+            raise ValueError("modes must hold MODE_2CP and only bits 0..3")
+        if not 0 <= int(extra) <= 64:
+            raise ValueError("extra must be in 0..64")
+        preds = pred_mask(modes)
+        nrefs, pr = self._check_result(result, preds, "affine_me_seeded")
+        if nrefs != len(refs):
+            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
+        ptrs = ((ctypes.c_void_p * 2) * 4)()
+        for r in range(nrefs):
+            for a in (0, 1):
+                if (preds >> (2 * a)) & 3:
+                    t = seeds.get((r, a)) if isinstance(seeds, dict) else None
+                    ptrs[r][a] = self._check_seed(t, a, f"seeds[{(r, a)}]", torch.int32, (2,)).data_ptr()
+        nbytes = lib().vame_seeded_work_bytes(self._h, nrefs, int(modes))
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_affine_me_seeded(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), int(modes), int(extra),
+                                          ptrs, ctypes.byref(pr), _ptr(work), work.numel() * 8, _ptr(bad),
+                                          self._stream()))
+        return result, bad
 
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to

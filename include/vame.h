@@ -357,6 +357,56 @@ typedef struct { vame_mv* mv[4][2]; int64_t* cost[4][2]; } vame_seed_result;   /
 int vame_seed_search(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
                      float lambda, int align_mask, int radius, const vame_seed_result* out, void* stream);
 
+/* The same seeds over a wide range, coarse to fine on a picture pyramid
+ * (DESIGN.md §16).  Level 0 of a frame is the frame; level l+1 at (x, y) is
+ * (a + b + c + d + 2) >> 2 of level l's samples at (2x, 2y), (2x+1, 2y),
+ * (2x, 2y+1), (2x+1, 2y+1); level l is (W >> l) x (H >> l).
+ * vame_seed_pyramid writes levels 1 and 2 of `frame` into pyr: caller memory
+ * (device, 8-byte aligned) of vame_seed_pyramid_bytes = 2*((W/2)*(H/2) +
+ * (W/4)*(H/4)) bytes (0 for a NULL context), level 1 directly followed by
+ * level 2, both dense and row-major.  A frame's pyramid is built once and
+ * reused for as long as the frame serves as cur or as a reference.  Argument
+ * errors (NULL, frame not 4-byte or pyr not 8-byte aligned): VAME_E_INVALID,
+ * nothing written.
+ *
+ * vame_seed_search_wide: outputs, masks, NULL rules and row layout as
+ * vame_seed_search; cur_pyr / ref_pyrs[r] are the pyramids of cur / refs[r].
+ * A row whose CU (x, y, w, h) is not wholly in the frame: mv = (0, 0), cost =
+ * INT64_MAX.  For the others, with L = levels:
+ *   displacement  d = (dx, dy) at level l stands for D = (dx << l, dy << l)
+ *   admissible    |Dx|, |Dy| <= radius, Dx <= W+7-x and Dy <= H+7-y; a
+ *                 candidate that is not admissible is never taken
+ *   value_l(d)    (SAD_l(d) << 2l) + floor(lambda * (bits + 2)): SAD_l over the
+ *                 block (x>>l, y>>l, w>>l, h>>l) of level l of cur against
+ *                 level l of the reference at the displaced position,
+ *                 coordinates clamped to [0, (W>>l)-1] x [0, (H>>l)-1]; bits =
+ *                 the search's bits of the 2-CP CPMVs LT = RT = (16Dx, 16Dy).
+ *                 value_0 is vame_seed_search's value
+ *   level L       candidates d in [-Rc, Rc]^2, Rc = radius >> L; the first
+ *                 minimum under strict < in the order (0, 0), then dy outer,
+ *                 dx inner
+ *   level l < L   (L-1 down to 0) centre c = 2 * (the winner of level l+1);
+ *                 candidates in order: at level 0 only D = (0, 0); then c;
+ *                 then c + (ex, ey), ey = -1, 0, 1 (outer), ex = -1, 0, 1
+ *                 (inner) without (0, 0); the first minimum under strict <
+ *   output        mv = (16Dx, 16Dy) of level 0's winner, cost = its value_0:
+ *                 what vame_seed_search assigns to that displacement, and
+ *                 never above the value of (0, 0)
+ * radius 0..128 (0: mv 0 and the value of (0, 0)), levels 1..2.  Reads nothing
+ * on the host, allocates and synchronizes nothing, runs on `stream` alone and
+ * can be captured; every output entry of an (r, alignment) in the mask is
+ * written by the call's kernels; integer sums only.  PROF does not enter.
+ * Argument errors (nrefs outside 1..4, an empty or unknown mask, radius or
+ * levels out of range, a NULL pyramid, a NULL output of an (r, alignment) in
+ * the mask, cur or a pyramid not 8-byte aligned, a reference not 4-byte
+ * aligned): VAME_E_INVALID, nothing written. */
+size_t vame_seed_pyramid_bytes(vame_ctx* ctx);
+int vame_seed_pyramid(vame_ctx* ctx, const uint16_t* frame, uint16_t* pyr, void* stream);
+int vame_seed_search_wide(vame_ctx* ctx, const uint16_t* cur, const uint16_t* cur_pyr,
+                          const uint16_t* const* refs, const uint16_t* const* ref_pyrs, int nrefs,
+                          float lambda, int align_mask, int radius, int levels,
+                          const vame_seed_result* out, void* stream);
+
 /* The search's iteration from caller-given CPMVs, on a CU list: the first
  * min(*ncus_dev, max_cus) descriptors (ncus_dev NULL: max_cus; a negative
  * count is 0); entries at or past the count are neither read nor written.

@@ -21,6 +21,7 @@
 #include "vame_birefine.h"
 #include "vame_search.h"
 #include "vame_seed.h"
+#include "vame_seed_pyr.h"
 
 #if VAME_SPLIT_TU
 namespace vame {
@@ -1206,6 +1207,61 @@ int vame_seed_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* re
   p.radius = radius;
   p.lambda = lambda;
   VAME_HIP(seed_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+size_t vame_seed_pyramid_bytes(vame_ctx* c) { return c ? 2 * pyr_samples(c->W, c->H) : 0; }
+
+int vame_seed_pyramid(vame_ctx* c, const uint16_t* frame, uint16_t* pyr, void* stream) {
+  if (!c || !frame || !pyr) return VAME_E_INVALID;
+  // the kernel reads frame rows as dwords and stores level-1 rows as 8-byte words
+  if ((reinterpret_cast<uintptr_t>(frame) & 3) || (reinterpret_cast<uintptr_t>(pyr) & 7)) return VAME_E_INVALID;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  SeedPyrDownParams p;
+  p.frame = frame;
+  p.pyr = pyr;
+  p.W = c->W;
+  p.H = c->H;
+  VAME_HIP(seed_pyr_down_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+int vame_seed_search_wide(vame_ctx* c, const uint16_t* cur, const uint16_t* cur_pyr, const uint16_t* const* refs,
+                          const uint16_t* const* ref_pyrs, int nrefs, float lambda, int align_mask, int radius,
+                          int levels, const vame_seed_result* out, void* stream) {
+  if (!c || !cur || !cur_pyr || !refs || !ref_pyrs || !out || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if ((align_mask & ~3) || !align_mask || radius < 0 || radius > kSeedWideMaxRadius || levels < 1 ||
+      levels > kSeedWideMaxLevels)
+    return VAME_E_INVALID;
+  // the kernels read block rows of cur and of the pyramids as 8-byte words and reference rows as dwords
+  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(cur_pyr)) & 7) return VAME_E_INVALID;
+  SeedWideParams p;
+  memset(&p, 0, sizeof(p));
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  for (int r = 0; r < nrefs; r++) {
+    if (!ref_pyrs[r] || (reinterpret_cast<uintptr_t>(ref_pyrs[r]) & 7)) return VAME_E_INVALID;
+    p.refPyrs[r] = ref_pyrs[r];
+    for (int a = 0; a < 2; a++) {
+      if (!((align_mask >> a) & 1)) continue;
+      if (!out->mv[r][a] || !out->cost[r][a]) return VAME_E_INVALID;
+      p.cost[r][a] = out->cost[r][a];
+      p.mv[r][a] = reinterpret_cast<int32_t*>(out->mv[r][a]);
+    }
+  }
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.curPyr = cur_pyr;
+  p.nrefs = nrefs;
+  p.W = c->W;
+  p.H = c->H;
+  p.nCtus = c->nCtus;
+  p.ctusPerRow = c->ctusPerRow;
+  p.radius = radius;
+  p.levels = levels;
+  p.lambda = lambda;
+  VAME_HIP(seed_wide_launch(p, (hipStream_t)stream));
   return VAME_OK;
 }
 

@@ -22,7 +22,8 @@ EXPORTS = (
     "vame_count_lines_ranges", "vame_set_max_pairs", "vame_get_max_pairs", "vame_affine_mc",
     "vame_affine_mc_dev", "vame_partition", "vame_partition_table", "vame_affine_mc_bi", "vame_bipred",
     "vame_partition_bi", "vame_bipred_refine", "vame_seed_search", "vame_affine_search",
-    "vame_seeded_work_bytes", "vame_affine_me_seeded",
+    "vame_seeded_work_bytes", "vame_affine_me_seeded", "vame_seed_pyramid_bytes", "vame_seed_pyramid",
+    "vame_seed_search_wide",
 )
 
 
@@ -72,6 +73,10 @@ def lib():
                                         P, P, P, P, P, P, P, P]
         L.vame_bipred_refine.argtypes = [P, P, P, I, P, I, P, F, I, P, P, P, P]
         L.vame_seed_search.argtypes = [P, P, P, I, F, I, I, ctypes.POINTER(SeedResult), P]
+        L.vame_seed_pyramid_bytes.argtypes = [P]
+        L.vame_seed_pyramid_bytes.restype = ctypes.c_size_t
+        L.vame_seed_pyramid.argtypes = [P, P, P, P]
+        L.vame_seed_search_wide.argtypes = [P, P, P, P, P, I, F, I, I, I, ctypes.POINTER(SeedResult), P]
         L.vame_affine_search.argtypes = [P, P, P, I, P, I, P, F, I, P, P, P, P]
         L.vame_seeded_work_bytes.argtypes = [P, I, I]
         L.vame_seeded_work_bytes.restype = ctypes.c_size_t

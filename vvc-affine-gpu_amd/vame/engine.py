@@ -531,6 +531,24 @@ class Engine:
             raise ValueError(f"{what} must be a contiguous {dtype} {(n,) + tail} tensor on {self.device}")
         return t
 
+    def _seed_out(self, nrefs: int, aligns: int, out: dict | None):
+        """(out, its vame_seed_result) of seed_search / seed_search_wide."""
+        if int(aligns) & ~3 or not int(aligns):
+            raise ValueError("aligns must hold bit 0 (FULL), bit 1 (HALF) or both")
+        keys = [(r, a) for r in range(nrefs) for a in (0, 1) if (aligns >> a) & 1]
+        if out is None:
+            out = {"mv": {k: torch.empty((self.n_cus(k[1]), 2), dtype=torch.int32, device=self.device) for k in keys},
+                   "cost": {k: torch.empty(self.n_cus(k[1]), dtype=torch.int64, device=self.device) for k in keys}}
+        sr = SeedResult()
+        for r, a in keys:
+            try:
+                mv, cost = out["mv"][(r, a)], out["cost"][(r, a)]
+            except (KeyError, TypeError):
+                raise ValueError(f"out['mv'] / out['cost'] miss {(r, a)}") from None
+            sr.mv[r][a] = self._check_seed(mv, a, f"out['mv'][{(r, a)}]", torch.int32, (2,)).data_ptr()
+            sr.cost[r][a] = self._check_seed(cost, a, f"out['cost'][{(r, a)}]", torch.int64, ()).data_ptr()
+        return out, sr
+
     def seed_search(self, cur, refs, lam: float, radius: int = 16, aligns: int = 3, out: dict | None = None):
         """vame_seed_search: the best integer displacement of every candidate
         CU inside +-radius (0..32) under SAD + the search's rate, first minimum
@@ -545,22 +563,64 @@ class Engine:
         refs, ref_ptrs = self._refs(refs, "seed_search")
         if not 0 <= int(radius) <= 32:
             raise ValueError("radius must be in 0..32")
-        if int(aligns) & ~3 or not int(aligns):
-            raise ValueError("aligns must hold bit 0 (FULL), bit 1 (HALF) or both")
-        keys = [(r, a) for r in range(len(refs)) for a in (0, 1) if (aligns >> a) & 1]
-        if out is None:
-            out = {"mv": {k: torch.empty((self.n_cus(k[1]), 2), dtype=torch.int32, device=self.device) for k in keys},
-                   "cost": {k: torch.empty(self.n_cus(k[1]), dtype=torch.int64, device=self.device) for k in keys}}
-        sr = SeedResult()
-        for r, a in keys:
-            try:
-                mv, cost = out["mv"][(r, a)], out["cost"][(r, a)]
-            except (KeyError, TypeError):
-                raise ValueError(f"out['mv'] / out['cost'] miss {(r, a)}") from None
-            sr.mv[r][a] = self._check_seed(mv, a, f"out['mv'][{(r, a)}]", torch.int32, (2,)).data_ptr()
-            sr.cost[r][a] = self._check_seed(cost, a, f"out['cost'][{(r, a)}]", torch.int64, ()).data_ptr()
+        out, sr = self._seed_out(len(refs), aligns, out)
         check(lib().vame_seed_search(self._h, _ptr(cur), ref_ptrs, len(refs), float(lam), int(aligns), int(radius),
                                      ctypes.byref(sr), self._stream()))
+        return out
+
+    def _pyr_samples(self) -> int:
+        return (self.W // 2) * (self.H // 2) + (self.W // 4) * (self.H // 4)
+
+    def _check_pyr(self, t, what: str):
+        if (t is None or t.dtype not in (torch.int16, torch.uint16) or tuple(t.shape) != (self._pyr_samples(),)
+                or t.device != self.device or not t.is_contiguous() or t.data_ptr() & 7):
+            raise ValueError(f"{what} must be a contiguous, 8-byte aligned int16/uint16 [{self._pyr_samples()}] tensor "
+                             f"on {self.device}")
+        return t
+
+    def seed_pyramid(self, frame, out=None):
+        """vame_seed_pyramid: levels 1 and 2 of the frame's 2:1 mean pyramid
+        (level l+1 = (a + b + c + d + 2) >> 2 of level l's 2x2 samples) as one
+        tensor [(W/2)(H/2) + (W/4)(H/4)] of the frame's dtype, level 1 followed
+        by level 2, both dense and row-major.  Build a frame's pyramid once and
+        pass it to seed_search_wide for as long as the frame is cur or a
+        reference.  out: a tensor of an earlier call to write into.
+        Asynchronous on the current stream."""
+        frame = self._frame(frame)
+        if out is None:
+            out = torch.empty(self._pyr_samples(), dtype=frame.dtype, device=self.device)
+        self._check_pyr(out, "out")
+        check(lib().vame_seed_pyramid(self._h, _ptr(frame), _ptr(out), self._stream()))
+        return out
+
+    def seed_search_wide(self, cur, refs, lam: float, radius: int = 64, levels: int = 2, aligns: int = 3,
+                         cur_pyr=None, ref_pyrs=None, out: dict | None = None):
+        """vame_seed_search_wide: seed_search's result over +-radius (0..128),
+        coarse to fine: every displacement of the grid of 2^levels samples
+        (levels 1..2) at the pyramid's top level, then +-1 around twice the
+        winner at every level below, down to the frame; at the frame (0, 0)
+        comes first, so a non-zero seed is strictly better than not moving.
+        The cost is seed_search's value of the returned displacement.
+        cur_pyr / ref_pyrs: the frames' seed_pyramid() tensors (ref_pyrs a
+        list, entries may be None); what is missing is built here.  Returns
+        the same dict as seed_search (affine_me_seeded takes out["mv"]).
+        Reads nothing on the host; asynchronous on the current stream."""
+        cur = self._frame(cur)
+        refs, ref_ptrs = self._refs(refs, "seed_search_wide")
+        if not 0 <= int(radius) <= 128:
+            raise ValueError("radius must be in 0..128")
+        if not 1 <= int(levels) <= 2:
+            raise ValueError("levels must be 1 or 2")
+        out, sr = self._seed_out(len(refs), aligns, out)
+        ref_pyrs = [None] * len(refs) if ref_pyrs is None else list(ref_pyrs)
+        if len(ref_pyrs) != len(refs):
+            raise ValueError(f"ref_pyrs holds {len(ref_pyrs)} pyramids, refs {len(refs)} frames")
+        cur_pyr = self.seed_pyramid(cur) if cur_pyr is None else self._check_pyr(cur_pyr, "cur_pyr")
+        ref_pyrs = [self.seed_pyramid(f) if t is None else self._check_pyr(t, f"ref_pyrs[{r}]")
+                    for r, (f, t) in enumerate(zip(refs, ref_pyrs))]
+        pyr_ptrs = (ctypes.c_void_p * len(refs))(*[t.data_ptr() for t in ref_pyrs])
+        check(lib().vame_seed_search_wide(self._h, _ptr(cur), _ptr(cur_pyr), ref_ptrs, pyr_ptrs, len(refs), float(lam),
+                                          int(aligns), int(radius), int(levels), ctypes.byref(sr), self._stream()))
         return out
 
     def affine_search(self, cus: torch.Tensor, refs, cur, lam: float, extra: int = 0,

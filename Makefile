@@ -36,7 +36,7 @@ KFLAGS_2CP := -mllvm -simplifycfg-sink-common=false -mllvm -simplifycfg-hoist-co
 # dependencies -- goes over this list: a new unit is one word here.
 UNITS := engine=vame_engine.hip=KFLAGS 2cp=vame_kernels_2cp.hip=KFLAGS_2CP mc=vame_mc.hip \
          partition=vame_partition.hip bipred=vame_bipred.hip birefine=vame_birefine.hip \
-         seed=vame_seed.hip seedpyr=vame_seed_pyr.hip search=vame_search.hip \
+         seed=vame_seed.hip search=vame_search.hip \
          hostlogic=vame_hostlogic.cpp io=vame_io.cpp
 unit_tag   = $(word 1,$(subst =, ,$(1)))
 unit_src   = $(CSRC)/$(word 2,$(subst =, ,$(1)))

@@ -215,3 +215,23 @@ def test_product_kernels_have_no_scratch():
             assert v == 0, (k, v)
         else:
             assert v <= 8, (k, v)
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"), reason="no llvm-readelf")
+def test_seed_kernels_are_the_seven_without_scratch():
+    """The seed searches are one unit with one grid kernel:
+    the library holds exactly seed_init_kernel, seed_grid_kernel<0 | 1 | 2>,
+    seed_close_kernel, seed_refine_kernel and seed_pyr_down_kernel, each with
+    a zero private segment.  Any other kernel whose name contains seed_ is a
+    stray instantiation or a second copy."""
+    sizes = kernel_scratch(_lib.LIB_PATH)
+    seed = {k: v for k, v in sizes.items() if "seed_" in k}
+    want = {"_ZN4vame16seed_init_kernelENS_10SeedParamsE",
+            "_ZN4vame16seed_grid_kernelILi0EEEvNS_10SeedParamsE",
+            "_ZN4vame16seed_grid_kernelILi1EEEvNS_10SeedParamsE",
+            "_ZN4vame16seed_grid_kernelILi2EEEvNS_10SeedParamsE",
+            "_ZN4vame17seed_close_kernelENS_10SeedParamsE",
+            "_ZN4vame18seed_refine_kernelENS_10SeedParamsE",
+            "_ZN4vame20seed_pyr_down_kernelENS_17SeedPyrDownParamsE"}
+    assert set(seed) == want, sorted(set(seed) ^ want)
+    assert not any(seed.values()), seed

@@ -21,7 +21,6 @@
 #include "vame_birefine.h"
 #include "vame_search.h"
 #include "vame_seed.h"
-#include "vame_seed_pyr.h"
 
 #if VAME_SPLIT_TU
 namespace vame {
@@ -1180,14 +1179,11 @@ int vame_bipred_refine(vame_ctx* c, const uint16_t* cur, const uint16_t* const* 
   return VAME_OK;
 }
 
-int vame_seed_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
-                     int align_mask, int radius, const vame_seed_result* out, void* stream) {
-  if (!c || !cur || !refs || !out || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
-  if ((align_mask & ~3) || !align_mask || radius < 0 || radius > kSeedMaxRadius) return VAME_E_INVALID;
-  // the kernel reads block rows of cur as 8-byte words and reference rows as dwords
-  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
-  SeedParams p;
-  memset(&p, 0, sizeof(p));
+// What vame_seed_search and vame_seed_search_wide share, after their own
+// argument checks: the references and the (refIdx, alignment) output mask into
+// the zeroed block, then its common fields and the launches.
+static int seed_search(vame_ctx* c, SeedParams& p, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                       float lambda, int align_mask, int radius, const vame_seed_result* out, void* stream) {
   if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
   for (int r = 0; r < nrefs; r++)
     for (int a = 0; a < 2; a++) {
@@ -1208,6 +1204,17 @@ int vame_seed_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* re
   p.lambda = lambda;
   VAME_HIP(seed_launch(p, (hipStream_t)stream));
   return VAME_OK;
+}
+
+int vame_seed_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                     int align_mask, int radius, const vame_seed_result* out, void* stream) {
+  if (!c || !cur || !refs || !out || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if ((align_mask & ~3) || !align_mask || radius < 0 || radius > kSeedMaxRadius) return VAME_E_INVALID;
+  // the kernel reads block rows of cur as 8-byte words and reference rows as dwords
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  SeedParams p;
+  memset(&p, 0, sizeof(p));  // levels 0, no pyramids
+  return seed_search(c, p, cur, refs, nrefs, lambda, align_mask, radius, out, stream);
 }
 
 size_t vame_seed_pyramid_bytes(vame_ctx* c) { return c ? 2 * pyr_samples(c->W, c->H) : 0; }
@@ -1236,33 +1243,17 @@ int vame_seed_search_wide(vame_ctx* c, const uint16_t* cur, const uint16_t* cur_
     return VAME_E_INVALID;
   // the kernels read block rows of cur and of the pyramids as 8-byte words and reference rows as dwords
   if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(cur_pyr)) & 7) return VAME_E_INVALID;
-  SeedWideParams p;
+  SeedParams p;
   memset(&p, 0, sizeof(p));
-  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  // all pyramids before refs and the output mask (once per reference in between them): every one of
+  // these returns VAME_E_INVALID before anything is launched, so the order cannot be seen
   for (int r = 0; r < nrefs; r++) {
     if (!ref_pyrs[r] || (reinterpret_cast<uintptr_t>(ref_pyrs[r]) & 7)) return VAME_E_INVALID;
     p.refPyrs[r] = ref_pyrs[r];
-    for (int a = 0; a < 2; a++) {
-      if (!((align_mask >> a) & 1)) continue;
-      if (!out->mv[r][a] || !out->cost[r][a]) return VAME_E_INVALID;
-      p.cost[r][a] = out->cost[r][a];
-      p.mv[r][a] = reinterpret_cast<int32_t*>(out->mv[r][a]);
-    }
   }
-  DeviceGuard guard(c->device);
-  VAME_HIP(guard.err);
-  p.cur = cur;
   p.curPyr = cur_pyr;
-  p.nrefs = nrefs;
-  p.W = c->W;
-  p.H = c->H;
-  p.nCtus = c->nCtus;
-  p.ctusPerRow = c->ctusPerRow;
-  p.radius = radius;
   p.levels = levels;
-  p.lambda = lambda;
-  VAME_HIP(seed_wide_launch(p, (hipStream_t)stream));
-  return VAME_OK;
+  return seed_search(c, p, cur, refs, nrefs, lambda, align_mask, radius, out, stream);
 }
 
 int vame_affine_search(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,

@@ -134,10 +134,10 @@ def merged(ref, cur, x, y, w, h, seed, lam, base2, base3=None, extra=0):
 def shifted_camera(nrefs=1):
     """The shifted-camera pair at 416x240, seed 0xBEEF: (refs [nrefs, H, W],
     cur) -- cur is POC 2 seen through a window moved by (-11, +6) samples,
-    refs[0] the QP-32 reconstruction of POC 0 (refs[1]: of POC 1)."""
+    refs[r] the QP-32 reconstruction of POC r (nrefs <= 4)."""
     from vame import synth
     W, H = 416, 240
-    big = {p: synth.synth_frame(W + 128, H + 128, p, 0xBEEF) for p in (0, 1, 2)}
+    big = {p: synth.synth_frame(W + 128, H + 128, p, 0xBEEF) for p in {0, 1, 2} | set(range(nrefs))}
     refs = [synth.recon_frame(big[p], p, 32, 0xBEEF)[64:64 + H, 64:64 + W] for p in range(nrefs)]
     cur = big[2][70:70 + H, 53:53 + W]
     return np.ascontiguousarray(np.stack(refs)).astype(np.uint16), np.ascontiguousarray(cur).astype(np.uint16)

@@ -69,6 +69,32 @@ def top_sads(ref, cur, boxes, Rc):
     return out
 
 
+def top_sads_tiles(ref, cur, boxes, Rc, tile):
+    """top_sads for boxes that cover little of the level: the same sums, one
+    tile of `tile` x `tile` samples (no box crosses a tile's border) and its
+    clamped reference window at a time, only the tiles that hold a box."""
+    H, W = cur.shape
+    ref, cur = ref.astype(np.int64), cur.astype(np.int64)
+    n = 2 * Rc + 1
+    out = np.zeros((len(boxes), n, n), np.int64)
+    key = (boxes[:, 1] // tile) * W + boxes[:, 0] // tile
+    for k in np.unique(key):
+        sel = np.nonzero(key == k)[0]
+        X0, Y0 = (boxes[sel[0], 0] // tile) * tile, (boxes[sel[0], 1] // tile) * tile
+        hh, ww = min(tile, H - Y0), min(tile, W - X0)
+        c = cur[Y0:Y0 + hh, X0:X0 + ww]
+        yy, xx = np.clip(np.arange(Y0 - Rc, Y0 + hh + Rc), 0, H - 1), np.clip(np.arange(X0 - Rc, X0 + ww + Rc), 0, W - 1)
+        win = ref[yy][:, xx]
+        x0, y0 = boxes[sel, 0] - X0, boxes[sel, 1] - Y0
+        x1, y1 = x0 + boxes[sel, 2], y0 + boxes[sel, 3]
+        I = np.zeros((hh + 1, ww + 1), np.int64)
+        for j in range(n):
+            for i in range(n):
+                I[1:, 1:] = np.abs(c - win[j:j + hh, i:i + ww]).cumsum(0).cumsum(1)
+                out[sel, j, i] = I[y1, x1] - I[y0, x1] - I[y1, x0] + I[y0, x0]
+    return out
+
+
 def sad9(ref, cur, x, y, w, h, cx, cy):
     """int64 [3, 3] at [ey + 1, ex + 1]: the SAD of the level's box against the
     level's reference displaced by (cx + ex, cy + ey), coordinates clamped."""
@@ -95,13 +121,19 @@ def admissible(Dx, Dy, x, y, W, H, radius):
 
 class Searcher:
     """The rule on one (ref, cur) pair.  SADs do not depend on lambda, radius
-    or (below the top) levels: they are kept between run() calls."""
+    or (below the top) levels: they are kept between run() calls.  rows: a set
+    of (align, row) that restricts the rows computed to those of it that lie
+    in the frame (the others stay (0, 0) / INF); None: every in-frame row.  A
+    restricted Searcher sums the top level CTU by CTU (top_sads_tiles), which
+    is what makes a few CTUs of a large frame affordable."""
 
-    def __init__(self, ref, cur):
+    def __init__(self, ref, cur, rows=None):
         self.ref, self.cur = pyramid(ref), pyramid(cur)
         self.H, self.W = cur.shape
         self.cands = {a: B.frame_candidates(self.W, self.H, a) for a in (0, 1)}
-        self.inn = {a: [c for c in self.cands[a] if c[1] + c[3] <= self.W and c[2] + c[4] <= self.H] for a in (0, 1)}
+        self.inn = {a: [c for c in self.cands[a] if c[1] + c[3] <= self.W and c[2] + c[4] <= self.H
+                        and (rows is None or (a, c[0]) in rows)] for a in (0, 1)}
+        self.restricted = rows is not None
         self._top, self._nine, self._zero = {}, {}, {}
 
     def top(self, align, L, Rc):
@@ -109,7 +141,10 @@ class Searcher:
         (both alignments in one pass over the displacements)."""
         if L not in self._top or (self._top[L].shape[1] - 1) // 2 < Rc:
             boxes = np.array([[c[1] >> L, c[2] >> L, c[3] >> L, c[4] >> L] for a in (0, 1) for c in self.inn[a]], np.int64)
-            self._top[L] = top_sads(self.ref[L], self.cur[L], boxes, Rc)
+            if self.restricted:
+                self._top[L] = top_sads_tiles(self.ref[L], self.cur[L], boxes, Rc, 128 >> L)
+            else:
+                self._top[L] = top_sads(self.ref[L], self.cur[L], boxes, Rc)
         n0 = len(self.inn[0])
         t = self._top[L][n0:] if align else self._top[L][:n0]
         big = (t.shape[1] - 1) // 2
@@ -202,3 +237,12 @@ def shifted_camera_wide(shift=(-43, 26), nrefs=1):
     refs = [synth.recon_frame(big[p], p, 32, 0xBEEF)[M:M + H, M:M + W] for p in range(nrefs)]
     cur = big[2][M + shift[1]:M + shift[1] + H, M + shift[0]:M + shift[0] + W]
     return np.ascontiguousarray(np.stack(refs)).astype(np.uint16), np.ascontiguousarray(cur).astype(np.uint16)
+
+
+def stripes(W=416, H=240):
+    """The tie input: (refs [2, H, W], cur) -- vertical stripes of period 16
+    with cur = refs[0] moved by 4 samples (refs[1]: by 8), so a CU's smallest
+    SAD is attained at every 16th dx and at every dy."""
+    x = np.arange(W + 16)
+    big = np.broadcast_to(np.where(x % 16 < 8, 900, 100).astype(np.uint16), (H, W + 16))
+    return np.ascontiguousarray(np.stack([big[:, :W], big[:, 12:W + 12]])), np.ascontiguousarray(big[:, 4:W + 4])

@@ -11,6 +11,7 @@ import torch
 
 import bipred_ref as B
 import seed_ref as S
+import seedpyr_ref as P
 from test_gpu_bipred import NAMES, SENTINEL, blank, dev, load
 from test_seed import inframe, sample
 from vame import mc as M
@@ -36,11 +37,14 @@ def eng():
 
 @functools.lru_cache(maxsize=None)
 def pairs():
-    """{name: (refs [n, H, W], cur)}: the shifted-camera pair (two references)
-    and s416_noise."""
-    z = load("s416_noise")
+    """{name: (refs [n, H, W], cur)}: the shifted-camera pair (two references),
+    s416_noise, the tie inputs (seedpyr_ref.stripes and s416_flat) and the
+    largest SAD there is (cur all 1023, the reference all 0)."""
+    z, flat = load("s416_noise"), load("s416_flat")
     refs, cur = S.shifted_camera(2)
-    return {"shifted": (refs, cur), "noise": (z["ref"][None], z["cur"])}
+    full = np.full((H, W), 1023, np.uint16)
+    return {"shifted": (refs, cur), "noise": (z["ref"][None], z["cur"]), "stripes": P.stripes(W, H),
+            "flat": (flat["ref"][None], flat["cur"]), "bound": (np.zeros((1, H, W), np.uint16), full)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -121,6 +125,78 @@ def test_seed_map_equals_seed_cu():
         if row in sad_maps("shifted", 0, 1):
             assert S.seed_from_map(sad_maps("shifted", 0, 1)[row], x, y, w, h, W, H, 3, LAM) == \
                 S.seed_cu(refs[0], cur, x, y, w, h, 3, LAM)
+
+
+# ------------------------------------------------------------------ 1b. ties and the largest SAD
+def tie_rows(name, align):
+    return seed_rows(align) if name == "stripes" else seed_rows(align)[::2]
+
+
+@functools.lru_cache(maxsize=None)
+def tie_maps(name, align):
+    """{row: sad_map at radius 32 against refs[0]} of the sampled in-frame rows."""
+    if name == "stripes":
+        return sad_maps(name, 0, align)
+    refs, cur = pairs()[name]
+    return {row: S.sad_map(refs[0], cur, x, y, w, h, 32) for row, x, y, w, h in tie_rows(name, align)
+            if x + w <= W and y + h <= H}
+
+
+@pytest.mark.parametrize("align", [0, 1])
+@pytest.mark.parametrize("name", ["stripes", "flat"])
+def test_ties_go_to_the_first_of_the_order(eng, name, align):
+    """lambda = 0 on inputs whose smallest SAD is attained many times: the
+    64-bit minimum of value << 15 | order over the dy workgroups must give
+    (0, 0) first, then dy outer, dx inner."""
+    drefs, dcur = dev_pair(name)
+    for radius in (3, 16, 32):
+        out = eng.seed_search(dcur, drefs[:1], 0.0, radius=radius)
+        torch.cuda.synchronize()
+        mv, cost = out["mv"][(0, align)].cpu().numpy(), out["cost"][(0, align)].cpu().numpy()
+        maps = tie_maps(name, align)
+        assert len(maps) >= 20
+        for row, x, y, w, h in tie_rows(name, align):
+            want = S.seed_from_map(maps[row], x, y, w, h, W, H, radius, 0.0) if row in maps else ((0, 0), INF)
+            assert (tuple(mv[row].tolist()), int(cost[row])) == want, (name, radius, align, row)
+        if name == "flat":  # one value everywhere: every in-frame row stays at (0, 0)
+            assert not mv.any() and (cost[[c[0] for c in inframe(align)]] < INF).all()
+
+
+def test_the_stripe_rows_tie():
+    """On the reference alone (the maps are those of the test above): at least
+    half of the sampled rows attain their minimum more than once inside every
+    radius, and not at (0, 0)."""
+    for radius in (3, 16, 32):
+        for align in (0, 1):
+            maps = tie_maps("stripes", align)
+            tied = moved = 0
+            for row, x, y, w, h in seed_rows(align):
+                if row not in maps:
+                    continue
+                m = maps[row][32 - radius:33 + radius, 32 - radius:33 + radius]
+                d = np.arange(-radius, radius + 1)
+                ok = (d[:, None] <= H + 7 - y) & (d[None, :] <= W + 7 - x)
+                tied += int((m[ok] == m[ok].min()).sum() > 1)
+                moved += S.seed_from_map(maps[row], x, y, w, h, W, H, radius, 0.0)[0] != (0, 0)
+            assert 2 * tied >= len(maps) and 2 * moved >= len(maps), (radius, align, tied, moved, len(maps))
+
+
+@pytest.mark.parametrize("lam", [0.0, LAM])
+def test_the_largest_sad_stays_inside_the_key(eng, lam):
+    """cur all 1023 against a reference of zeros: every displacement of a CU
+    costs 1023 w h, the 128x128 CU 16,760,832 -- just under the 2^25 the key's
+    layout relies on -- and (0, 0) comes first."""
+    drefs, dcur = dev_pair("bound")
+    zero = B.rate(B.bits_of(2, [0] * 6) + 2, lam)
+    assert 1023 * 128 * 128 == 16760832 < 1 << 25
+    for out in (eng.seed_search(dcur, drefs, lam, radius=32), eng.seed_search_wide(dcur, drefs, lam, radius=128, levels=2)):
+        torch.cuda.synchronize()
+        for align in (0, 1):
+            cands = B.frame_candidates(W, H, align)
+            want = np.array([1023 * w * h + zero if x + w <= W and y + h <= H else INF for _, x, y, w, h in cands], np.int64)
+            assert not out["mv"][(0, align)].any()
+            np.testing.assert_array_equal(out["cost"][(0, align)].cpu().numpy(), want)
+        assert (out["cost"][(0, 0)] == 16760832 + zero).sum() == 3  # the 128x128 CUs of the three CTUs wholly in the frame
 
 
 def raw_seed(eng, name, mask, radius, mv, cost, nrefs=None, h=None, null=(), lam=LAM):

@@ -84,3 +84,27 @@ def test_the_wide_shift_is_found():
     got = int(wide(64, 2, 0)[1][rows].sum())
     print("zero", zero, "radius 64 levels 2", got, got / zero)
     assert 5 * got <= zero
+
+
+def test_a_restricted_searcher_equals_the_unrestricted_on_its_rows():
+    """Searcher(rows=) restricts the rows computed and nothing else: on its
+    rows the unrestricted mv and cost, every other row (0, 0) / INF."""
+    s = searcher()
+    rows = {(a, c[0]) for a in (0, 1) for c in sample(a, 24, salt=17)}
+    rows |= {(a, c[0]) for a in (0, 1) for c in B.frame_candidates(W, H, a)[-5:]}  # rows that leave the frame
+    few = P.Searcher(s.ref[0], s.cur[0], rows=rows)
+    for radius, levels in ((64, 2), (37, 1)):
+        for align in (0, 1):
+            mv, cost, facts = few.run(LAM, radius, levels, align)
+            wmv, wcost, wfacts = wide(radius, levels, align)
+            mine = np.array(sorted(r for a, r in rows if a == align))
+            assert 20 <= len(mine) < len(wcost) // 10
+            np.testing.assert_array_equal(mv[mine], wmv[mine])
+            np.testing.assert_array_equal(cost[mine], wcost[mine])
+            other = np.setdiff1d(np.arange(len(wcost)), mine)
+            assert not mv[other].any() and (cost[other] == P.INF).all()
+            assert (wcost[mine] < P.INF).sum() >= 20 and (wcost[mine] == P.INF).sum() == 5
+            assert facts["outside"] == set(other.tolist()) | wfacts["outside"]  # 'outside' is what is not computed
+            for k in facts:
+                if k != "outside":
+                    assert facts[k] == wfacts[k] & set(mine.tolist()), k

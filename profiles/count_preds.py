@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Executed fraction of the algorithmic sub-block predictions (the exact early
-exit of vame_kernel.h skips the rest), per kernel class, on one step of a
+exit of vame_dev.h skips the rest), per kernel class, on one step of a
 bench config, with the instrumentation build (make count):
 
     VAME_LIB=vvc-affine-gpu_amd/lib/libvame_count.so python3 profiles/count_preds.py --config c2

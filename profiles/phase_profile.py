@@ -2,7 +2,7 @@
 
 Runs a bench config's step through the profiling-only build
 `vvc-affine-gpu_amd/lib/libvame_phase.so` (`make phase`: every wave sums the
-shader clock per phase, vame_kernel.h VAME_PHASE_TIMING) and prints, per
+shader clock per phase, vame_instr.h VAME_PHASE_TIMING) and prints, per
 kernel class and pass, the share of wave cycles in each phase -- staging,
 prediction (+ SATD), cost, gradient sums, equation reduction, solve + CPMV
 update, results -- where a phase includes the wait at the barrier that ends it; the

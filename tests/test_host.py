@@ -122,11 +122,14 @@ def test_pair_accounting_matches_survey():
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-@pytest.mark.parametrize("defs", [["-DVAME_ABLATE=63"], ["-DVAME_DUP=23"], ["-DVAME_PHASE_TIMING=1"], ["-DVAME_COUNT_PRED=1"]],
-                         ids=["ablate", "dup", "phase", "count"])
+@pytest.mark.parametrize("defs", [["-DVAME_ABLATE=63"], ["-DVAME_DUP=23"], ["-DVAME_PHASE_TIMING=1"], ["-DVAME_COUNT_PRED=1"],
+                                  ["-DVAME_DUP=4063"], ["-DVAME_ABLATE=3903"]],
+                         ids=["ablate", "dup", "phase", "count", "dup-all", "ablate-all"])
 def test_instrumentation_builds_compile(tmp_path, defs):
     """The timing-only / profiling builds (make ablate / variant / phase; the
-    only compile-time switches the kernel keeps) still compile for gfx950."""
+    only compile-time switches the kernel keeps) still compile for gfx950;
+    dup-all / ablate-all: every VAME_DUP block in both passes (4063) and every
+    VAME_ABLATE bit the device code reads (3903: bits 0-5 and 8-11)."""
     import subprocess
     src = os.path.join(os.path.dirname(__file__), "..", "vvc-affine-gpu_amd", "csrc", "vame_engine.hip")
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17",

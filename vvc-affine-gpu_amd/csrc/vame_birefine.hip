@@ -12,7 +12,7 @@
 // 2 cur - P_fixed; in LDS: the moving hypothesis' samples P_m as int16 [h][w]
 // (2 / 8 / 32 KB) for the Sobel neighbourhood, the 24 int64 moments and the
 // 6x7 FP64 system.  Every step of the iteration is the search's device
-// function (vame_kernel.h): mv_field, filter_rows_global, satd_4x4, grad_sb,
+// function (vame_dev.h): mv_field, filter_rows_global, satd_4x4, grad_sb,
 // eq_value, seg_solve, scale_delta; the gradient step and the workgroup sums
 // are vame_refine_core.h's, shared with vame_search.hip.
 //

@@ -17,6 +17,7 @@
 #include "../../include/vame.h"
 #include "vame_kernel.h"
 #include "vame_mc_core.h"
+#include "vame_partition.h"
 #include "vame_bipred.h"
 #include "vame_birefine.h"
 #include "vame_search.h"
@@ -1559,7 +1560,7 @@ const char* vame_last_hip_error(void) { return g_hip_err; }
 
 #if VAME_PHASE_TIMING
 // profiling-only builds: per-phase shader-clock sums [kernel: quad, ctu, half,
-// ctu2, half2w, half2h][kPhSlots] (see vame_kernel.h)
+// ctu2, half2w, half2h][kPhSlots] (see vame_instr.h)
 int vame_debug_phase_cycles(unsigned long long* out, int reset) {
   if (!out) return VAME_E_INVALID;
   VAME_HIP(hipDeviceSynchronize());
@@ -1576,7 +1577,7 @@ int vame_debug_phase_cycles(unsigned long long* out, int reset) {
 // them whose window left the staged tile, [2 + quad 2-CP, quad 3-CP, ctu 2-CP,
 // ctu 3-CP], and of those the ones a 4 / 8 / 16 px wider margin would hold,
 // [6 + quad x3, ctu x3], then the wave lane slots [12 + kernel], [14 + kernel],
-// [16 + kernel] (see vame_kernel.h)
+// [16 + kernel] (see vame_instr.h)
 int vame_debug_pred_count(unsigned long long* out20, int reset) {
   if (!out20) return VAME_E_INVALID;
   VAME_HIP(hipDeviceSynchronize());

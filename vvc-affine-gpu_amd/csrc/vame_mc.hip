@@ -1,6 +1,6 @@
 // vame_mc.hip -- affine motion compensation of caller-given CPMVs
 // (vame_affine_mc, include/vame.h): the prediction and the cost of one
-// prediction step of the search (vame_kernel.h: mv_field, filter_rows_global,
+// prediction step of the search (vame_dev.h: mv_field, filter_rows_global,
 // prof_refine, satd_4x4, affine_bits), for any list of CUs.
 //
 // Work mapping: one lane per 4x4 sub-block over the

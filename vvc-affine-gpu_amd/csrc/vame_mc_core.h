@@ -3,7 +3,7 @@
 // the CU descriptors and their validity rule, the concatenation of the valid
 // descriptors' sub-blocks (scan, count, offsets, launch), and one hypothesis:
 // the search's prediction of a 4x4 sub-block from CPMVs up to its second-stage
-// accumulators, bit-exact with predict_sb (vame_kernel.h) (DESIGN.md §11, §13,
+// accumulators, bit-exact with predict_sb (vame_dev.h) (DESIGN.md §11, §13,
 // §14).
 //
 // What is here is what could move without changing the code the compiler
@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "vame_kernel.h"
+#include "vame_dev.h"
 
 namespace vame {
 
@@ -192,11 +192,6 @@ __device__ __forceinline__ int row_sum16(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);  // row_half_mirror
   v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);  // row_mirror
   return v;
-}
-
-// floor(lambda * bits), the search's rate term (affine.cl:442-446)
-__device__ __forceinline__ long long mc_rate(float lambda, int bits) {
-  return (long long)(int)floorf(__fmul_rn(lambda, (float)bits));
 }
 
 // ----------------------------------------------------------------- hypothesis

@@ -31,6 +31,7 @@
 
 #include "../../include/vame.h"
 #include "vame_mc_core.h"
+#include "vame_partition.h"
 
 namespace vame {
 

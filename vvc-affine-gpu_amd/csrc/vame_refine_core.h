@@ -4,8 +4,8 @@
 // sub-block (SB of them in the largest class), the prediction samples P_m of
 // the moving CPMVs in LDS.  Here are the workgroup sums and one gradient step
 // -- Sobel gradients on P_m, the moments, solveEqual, scaleDeltaMvs, the
-// wrapping add, the clamp to +-2^17 and clipMv -- built from the search's
-// device functions (vame_kernel.h).  The error term is e = E - P_m: E is
+// wrapping add, the clamp to +-2^17 and clipMv (update_cpmv) -- built from the
+// search's device functions (vame_dev.h).  The error term is e = E - P_m: E is
 // 2 cur - P_fixed for a bi descriptor and cur for a uni one.
 #pragma once
 #include "vame_mc_core.h"
@@ -106,10 +106,7 @@ __device__ __forceinline__ bool br_step(const uint2* s_pm, const uint2 (&E)[SB][
   for (int j = 0; j < 6; j++) {
     if (j < 2 * ncp) {
       const double d = s_M[j == 1 ? 2 : j == 2 ? 1 : j];  // LT = (d0, d2), RT = (d1, d3), LB = (d4, d5)
-      int v = (int)((unsigned)cc[j] + (unsigned)scale_delta(d));
-      v = clampi(v, kMvMin, kMvMax);
-      const int pos = (j & 1) ? g.y : g.x, lim = (j & 1) ? H : W;
-      v = clampi(v, shl(-128 - 8 - pos + 1, 4), shl(lim + 8 - pos - 1, 4));  // clipMv
+      const int v = update_cpmv(cc[j], d, (j & 1) ? g.y : g.x, (j & 1) ? H : W);
       moved = moved || v != cc[j];
       cc[j] = v;
     }

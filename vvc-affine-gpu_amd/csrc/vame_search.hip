@@ -192,14 +192,8 @@ __global__ __launch_bounds__(kSeededThreads) void seeded_lb_kernel(SeededParams 
   McCu cu = p.work.cus2[k];
   const int lw = 31 - __clz(cu.w), lh = 31 - __clz(cu.h);
   // affine.cl:81-105, as the fused search derives its 3-CP start
-  const int sh = 7 + lh - lw;
-  int vx2 = shl(cu.ltx, 7) - shl(cu.rty - cu.lty, sh);
-  int vy2 = shl(cu.lty, 7) + shl(cu.rtx - cu.ltx, sh);
-  vx2 = (vx2 + 64 - (vx2 >= 0)) >> 7;
-  vy2 = (vy2 + 64 - (vy2 >= 0)) >> 7;
-  int lbx = shl(to_quarter(clampi(vx2, kMvMin, kMvMax)), 2);
-  int lby = shl(to_quarter(clampi(vy2, kMvMin, kMvMax)), 2);
-  clip_mv(lbx, lby, cu.x, cu.y, p.search.W, p.search.H);
+  int lbx, lby;
+  derive_lb(cu.ltx, cu.lty, cu.rtx, cu.rty, lw, lh, cu.x, cu.y, p.search.W, p.search.H, lbx, lby);
   cu.ncps = 3;
   cu.lbx = lbx;
   cu.lby = lby;

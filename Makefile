@@ -34,7 +34,8 @@ KFLAGS_2CP := -mllvm -simplifycfg-sink-common=false -mllvm -simplifycfg-hoist-co
 # The library's units, one word each: <object tag>=<source>[=<variable with its
 # own flags>].  Everything below -- build_lib, resource-usage, the
 # dependencies -- goes over this list: a new unit is one word here.
-UNITS := engine=vame_engine.hip=KFLAGS 2cp=vame_kernels_2cp.hip=KFLAGS_2CP mc=vame_mc.hip \
+UNITS := engine=vame_engine.hip=KFLAGS 2cp=vame_kernels_2cp.hip=KFLAGS_2CP stages=vame_stages.hip \
+         pack=vame_pack.hip=KFLAGS templates=vame_templates.cpp mc=vame_mc.hip \
          partition=vame_partition.hip bipred=vame_bipred.hip birefine=vame_birefine.hip \
          seed=vame_seed.hip search=vame_search.hip \
          hostlogic=vame_hostlogic.cpp io=vame_io.cpp

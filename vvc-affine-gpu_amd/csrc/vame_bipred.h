@@ -2,19 +2,11 @@
 // include/vame.h): vame_bipred's parameter block and launch
 // function (vame_affine_mc_bi's are vame_mc_core.h's McBiParams, mc_bi_launch).
 #pragma once
+#include "vame_items.h"
 #include "vame_mc_core.h"
 
 namespace vame {
 
-// A candidate CU of the frame's fixed geometry that lies wholly in the frame
-// (vame_create builds the table: the aligned candidates first, CTUs ascending,
-// rows ascending, then the half-aligned ones).
-struct BiCand {
-  int32_t xy;     // frame x | y << 16
-  int32_t shape;  // log2 w | log2 h << 4 | align << 8
-  int32_t row;    // ctu * {201 | 284} + offset: the row in its alignment's arrays
-  int32_t first;  // its first group of 16 sub-blocks (over both alignments)
-};
 constexpr int kBiPairs = 6;  // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
 
 struct BiRowsParams {

@@ -223,28 +223,12 @@ const char* kPredTag[4] = {"_FULL_2CPs_", "_FULL_3CPs_", "_HALF_2CPs_", "_HALF_3
 const char* kHeader = "POC,List,Ref,CTU,idx,X,Y,Cost,LT_X,LT_Y,RT_X,RT_Y,LB_X,LB_Y\n";
 
 std::string size_name(int align, int g) {
-  const int w = align ? kHalfW[g] : kFullW[g], h = align ? kHalfH[g] : kFullH[g];
-  return std::to_string(w) + "x" + std::to_string(h);
+  const CuGeom c = cu_geom(align, g, 0);
+  return std::to_string(c.w) + "x" + std::to_string(c.h);
 }
 
 std::string log_path(const char* prefix, int pred, int g) {
   return std::string(prefix) + kPredTag[pred] + size_name(pred >> 1, g) + ".csv";
-}
-
-// CU position inside the frame, as the log writer computes it
-// (main_aux_functions.h:460-479): FULL = raster order of the size, HALF = the
-// host tables HA_ALL_X_POS / HA_ALL_Y_POS (constants.h:327-364, equal to the
-// kernel tables restated in vame_tables.h).
-inline void cu_pos(int align, int g, int cu, int ctu, int ctuCols, int& x, int& y) {
-  if (!align) {
-    y = (cu * kFullW[g]) / 128 * kFullH[g];
-    x = (cu * kFullW[g]) % 128;
-  } else {
-    y = kHalfY8[g][cu] * 8;
-    x = kHalfX8[g][cu] * 8;
-  }
-  y += (ctu / ctuCols) * 128;
-  x += (ctu % ctuCols) * 128;
 }
 
 // Decimal text of an integer, as printf's %d / %ld: two digits per step from
@@ -297,8 +281,7 @@ struct Buf {
 
 void format_rows(Buf& buf, int align, int g, int ctu0, int ctu1, int ctuCols, int poc,
                  int ref, const int64_t* cost, const vame_cpmvs* cp) {
-  const int ncu = align ? kHalfN[g] : (kFullStride[g + 1] - kFullStride[g]);
-  const int stride = align ? kHalfStride[g] : kFullStride[g];
+  const int ncu = group_cus(align, g), stride = group_stride(align, g);
   const int T = align ? kHalfCusPerCtu : kFullCusPerCtu;
   // a row is at most 4 x 11 + 3 x 5 + 20 + 6 x 11 + 14 separators < 160 bytes
   char* const p0 = buf.reserve((size_t)(ctu1 - ctu0) * ncu * 160);
@@ -313,8 +296,11 @@ void format_rows(Buf& buf, int align, int g, int ctu0, int ctu1, int ctuCols, in
   const size_t npre = (size_t)(pe - pre);
   for (int ctu = ctu0; ctu < ctu1; ctu++) {
     for (int cu = 0; cu < ncu; cu++) {
-      int x, y;
-      cu_pos(align, g, cu, ctu, ctuCols, x, y);
+      // the CU's position in the frame, as the reference's log writer computes
+      // it (main_aux_functions.h:460-479: FULL the raster order of the size,
+      // HALF its tables HA_ALL_X_POS / HA_ALL_Y_POS)
+      const CuGeom pos = cu_geom(align, g, cu);
+      const int x = pos.x + ctu % ctuCols * kCtu, y = pos.y + ctu / ctuCols * kCtu;
       const size_t i = (size_t)ctu * T + stride + cu;
       memcpy(p, pre, npre);
       p += npre;

@@ -1,5 +1,5 @@
 // vame_kernel.h -- the search kernel of the affine-ME hot path (HIP, CDNA4):
-// its launch parameters and work-item descriptors, its LDS layout, the
+// its launch parameters, its LDS layout, the
 // reduction of the normal equations, the kernel body and the kernels.  The
 // device functions it is built from are in vame_dev.h, the instrumentation
 // switches in vame_instr.h.  Only vame_engine.hip and vame_kernels_2cp.hip
@@ -34,7 +34,7 @@
 //     for 2 CP, 24 moments for 3 CP) with DPP segment reductions and solved by
 //     the CU's lanes with the reference's double-precision elimination,
 //     operation for operation.
-// Two scheduling modes per work item (chosen on the host, vame_engine.hip):
+// Two scheduling modes per work item (chosen on the host, vame_templates.cpp):
 //   autonomous  every CU has <= 64 lanes and is owned by ONE wave; each wave
 //               iterates its CUs on its own (wave-local LDS ordering only, no
 //               workgroup barrier inside the iteration loop);
@@ -56,41 +56,9 @@
 #include <hip/hip_runtime.h>
 
 #include "vame_dev.h"
+#include "vame_items.h"
 
 namespace vame {
-
-constexpr int kMaxCu = 16;    // CU state slots per workgroup (LDS)
-constexpr int kMaxTasks = 16;  // autonomous items: wave tasks (wave w runs tasks w, w + 4, ...)
-constexpr int kTaskCu = 4;    // CUs per wave task (<= 64 sub-blocks, >= 16 each)
-constexpr int kItemCu = kMaxTasks * kTaskCu;  // CU slots per work item
-constexpr int kThreads = 256;  // quadrant workgroups
-
-struct CuSlot {          // 8 bytes
-  uint8_t x, y;          // CTU-relative position
-  uint8_t lw : 4, lh : 4;  // log2 width / height
-  uint8_t align : 1;     // 0 FULL, 1 HALF
-  uint8_t taskCus : 5;   // a task's first slot: CUs in the task (0 elsewhere)
-  uint16_t outOff : 9;   // RETURN_STRIDE[group] + cuIdx
-  uint16_t taskLogL : 4;  // a task's first slot: log2 lanes per CU
-  uint16_t pad;
-};
-static_assert(sizeof(CuSlot) == 8, "CuSlot packing");
-
-// An item's CUs come in tasks of one CU size each, run over the item's one
-// staged tile: a cooperative item's tasks one after another by the whole
-// workgroup, an autonomous item's tasks by its waves (wave w: tasks w, w + 4).
-// Task t holds CU slots t * kTaskCu .. (a single-task cooperative item: up to
-// kMaxCu slots from 0).
-struct Item {
-  int16_t nCu;      // CU slots (host view; unused slots have lw 0)
-  int16_t rx, ry;   // region origin (CTU-relative)
-  int16_t coop;     // bit 0: cooperative (a task's CUs span waves); bit 1: autonomous waves claim tasks;
-                    // bit 2: two stacked sub-blocks per lane (affine_me_quad's SBL2 items)
-  int16_t nTasks;
-  int16_t rw, rh;   // affine_me_half items: the region's extent (the CU's); 0 elsewhere
-  int16_t pad;
-  CuSlot cu[kItemCu];
-};
 
 // One (POC, refIdx) pair of a launch: the reference's kernel arguments for it
 // (affine.cl:11 / :960: frames, lambda, result arrays per PRED).
@@ -149,53 +117,6 @@ struct CuState {
   int32_t bestHasS;  // 2-CP pass: the best CPMVs' gradient sums are in s_bestS
   int32_t seedSkip;  // 3-CP pass: iteration 0 reuses the 2-CP winner's prediction
   int32_t pad;
-};
-
-// Work-item classes (kernels): 0 affine_me_quad -- a 64x64 quadrant, 256
-// threads; 1 affine_me_ctu -- a whole 128x128 CTU, 1024 threads; 2
-// affine_me_half -- ONE 128x64 or 64x128 CU, 512 threads (two workgroups per
-// CU: one's single-wave solve overlaps the other's prediction), its tile
-// staged over the CU's extent only (160 x 96 or 96 x 160 of the square
-// storage).
-// 3 affine_me_ctu2 -- ONE 128x128 CU per 512-thread workgroup, two
-// vertically adjacent sub-blocks per lane, two workgroups per CU (one's
-// single-wave cost and solve phases overlap the other's prediction).
-// 4 / 5 affine_me_half2w / affine_me_half2h -- ONE 128x64 / 64x128 CU per
-// 256-thread workgroup, two stacked sub-blocks per lane, its tile staged over
-// the CU's extent (160 x 96 / 96 x 160, sized for it), four workgroups per CU.
-// 6 affine_me_quad2 -- a 64x64 quadrant's CUs of 32 to 128 sub-blocks, 256
-// threads, two stacked sub-blocks per lane, autonomous wave tasks only (a CU
-// of 32 / 64 / 128 sub-blocks on 16 / 32 / 64 lanes, four / two / one per
-// wave): every per-wave step of an iteration (MV field, cost, equation
-// reduction, solve, update) covers twice the sub-blocks it does in
-// affine_me_quad, which keeps the 16-sub-block CUs and the 64x64 CUs.
-enum { kKindQuad = 0, kKindCtu = 1, kKindHalf = 2, kKindCtu2 = 3, kKindHalf2W = 4, kKindHalf2H = 5, kKindQuad2 = 6 };
-template <int KIND>
-struct Cfg {
-  static constexpr bool HALF2 = KIND == kKindHalf2W || KIND == kKindHalf2H;
-  static constexpr bool QUAD = KIND == kKindQuad || KIND == kKindQuad2;  // quadrant work items
-  static constexpr int REGION = QUAD ? 64 : 128;  // largest region edge
-  static constexpr int THREADS = QUAD || HALF2 ? 256 : KIND == kKindCtu ? 1024 : 512;
-  static constexpr int SBL = KIND == kKindCtu2 || HALF2 || KIND == kKindQuad2 ? 2 : 1;  // sub-blocks per lane (stacked vertically)
-  static constexpr int MAXCU = (KIND == kKindHalf || KIND == kKindCtu2 || HALF2) ? 1 : kMaxCu;  // CU state slots (LDS)
-  static constexpr int ITEMCU = QUAD ? kItemCu : MAXCU;  // CU slots per item
-  static constexpr bool AUTO = QUAD;                    // holds autonomous items
-  static constexpr bool COOP = KIND != kKindQuad2;      // holds cooperative items
-  static constexpr int MARGIN = 16;                     // reference-tile margin (samples)
-  static constexpr int TILE = REGION + 2 * MARGIN;      // tile edge (samples; the staged extent's largest)
-  static constexpr int TILE_W = KIND == kKindHalf2H ? 64 + 2 * MARGIN : TILE;  // allocated tile extent
-  static constexpr int TILE_H = KIND == kKindHalf2W ? 64 + 2 * MARGIN : TILE;
-  // tile pitch (samples) == 8 (mod 16): the window rows of sub-blocks 4 rows
-  // apart land 16 banks apart (2-way at most for the packed-pair reads)
-  static constexpr int TP = (TILE_W + 7) / 16 * 16 + 8;
-  static constexpr int TILE_ELEMS = TILE_H * TP + 16;
-  static constexpr int NSB = THREADS * SBL;             // sub-blocks per work item (max)
-  // SBL = 2: the upper sub-block's prediction parked in LDS across the lower
-  // one's (held in registers: +3 % time at c4); affine_me_half2* keep it in
-  // registers, so that four workgroups fit a CU's LDS (parked in LDS, three
-  // per CU: 8 % slower, HISTORY.md), and so does affine_me_quad2 (parked in
-  // LDS it loses a workgroup per CU: 3 % slower at c2, 5 % at c4, HISTORY.md)
-  static constexpr bool STASH = KIND != kKindQuad2 && !HALF2;
 };
 
 // Segment sums over aligned segments of 2^LOGS lanes (LOGS <= 6; the host packs

@@ -1,5 +1,5 @@
 // vame_partition.h -- the partition decision's parameter block and launch
-// (vame_partition.hip; called by vame_engine.hip).
+// (vame_partition.hip; called by vame_stages.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -97,6 +97,20 @@ constexpr uint8_t kHalfY8[kHalfGroups][32] = {
     {1, 1, 1, 1, 1, 1, 3, 3, 3, 3, 5, 5, 5, 5, 5, 5,
      9, 9, 9, 9, 9, 9, 11, 11, 11, 11, 13, 13, 13, 13, 13, 13}};
 
+// CU k of size group g of an alignment (0 FULL, 1 HALF): the group's CU count
+// and first output offset, and the CU's CTU-relative position and size.  Every
+// enumeration of a group's CUs on the host goes through here.
+VAME_HD inline int group_cus(int align, int g) { return align ? kHalfN[g] : kFullStride[g + 1] - kFullStride[g]; }
+VAME_HD inline int group_stride(int align, int g) { return align ? kHalfStride[g] : kFullStride[g]; }
+struct CuGeom {
+  int x, y, w, h;
+};
+VAME_HD inline CuGeom cu_geom(int align, int g, int k) {
+  if (align) return {kHalfX8[g][k] * 8, kHalfY8[g][k] * 8, kHalfW[g], kHalfH[g]};
+  const int w = kFullW[g], h = kFullH[g], cols = kCtu / w;
+  return {k % cols * w, k / cols * h, w, h};
+}
+
 // ---- 6-tap affine luma filter, taps 1..6 of the 8-tap table (taps 0 and 7 are
 // zero for every phase), one int8 per tap, phase-major.
 constexpr int8_t kLuma6[16][6] = {

@@ -35,6 +35,17 @@ def _ptr(t: torch.Tensor | None):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _poc_result(res: dict) -> PocResult:
+    """The vame_poc_result of an alloc_poc dict: the pointers of every
+    (refIdx, MODE) entry it holds."""
+    pr = PocResult()
+    for (r, name), (cost, cpmv) in res.items():
+        m = MODES.index(name)
+        pr.cost[r][m] = cost.data_ptr()
+        pr.cpmvs[r][m] = cpmv.data_ptr()
+    return pr
+
+
 class Engine:
     def __init__(self, width: int, height: int, device: int | torch.device = 0):
         if not torch.cuda.is_available():
@@ -151,6 +162,21 @@ class Engine:
         self._check_scalar(ncus, "ncus")
         return cur if want_cost else None, ref_ptrs, len(refs)
 
+    def _refine_out(self, cus: torch.Tensor, out, cost):
+        """The out / cost buffers of affine_search and bipred_refine for the
+        descriptors `cus`: the caller's, checked, or new ones."""
+        n, cols = cus.shape
+        if out is None:
+            out = torch.empty_like(cus)
+        else:
+            self._check_cus(out, cols, "out", n)
+        if cost is None:
+            cost = torch.empty(n, dtype=torch.int64, device=self.device)
+        elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
+              or not cost.is_contiguous()):
+            raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
+        return out, cost
+
     def _check_out(self, out, align: int):
         """Caller-supplied result buffers must hold exactly the launch's rows:
         int64 cost[n], int32 cpmv[n, 7], contiguous, on the engine's device."""
@@ -213,11 +239,7 @@ class Engine:
             cur = self._frame(cur)
             refs = [self._frame(r) for r in refs]
             self._check_poc_out(out, len(refs), modes)
-            pr = PocResult()
-            for (r, name), (cost, cpmv) in out.items():
-                m = MODES.index(name)
-                pr.cost[r][m] = cost.data_ptr()
-                pr.cpmvs[r][m] = cpmv.data_ptr()
+            pr = _poc_result(out)
             ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
             keep += [cur, refs, pr, ref_ptrs]
             arr[j].cur = cur.data_ptr()
@@ -248,11 +270,7 @@ class Engine:
         for j, res in enumerate(results):
             nrefs = max(r for r, _ in res) + 1
             self._check_poc_out(res, nrefs, modes)
-            pr = PocResult()
-            for (r, name), (cost, cpmv) in res.items():
-                m = MODES.index(name)
-                pr.cost[r][m] = cost.data_ptr()
-                pr.cpmvs[r][m] = cpmv.data_ptr()
+            pr = _poc_result(res)
             keep.append(pr)
             arr[j].nrefs = nrefs
             arr[j].out = ctypes.cast(ctypes.pointer(pr), ctypes.c_void_p)
@@ -339,16 +357,14 @@ class Engine:
         nrefs = max(r for r, _ in result) + 1
         if not 1 <= nrefs <= 4:
             raise ValueError(f"{what} takes the results of 1..4 references")
-        pr = PocResult()
+        need = {}
         for r in range(nrefs):
             for m, name in enumerate(MODES):
                 if (preds >> m) & 1:
                     if (r, name) not in result:
                         raise ValueError(f"result buffers missing for {(r, name)}")
-                    cost, cpmv = self._check_out(result[(r, name)], m >> 1)
-                    pr.cost[r][m] = cost.data_ptr()
-                    pr.cpmvs[r][m] = cpmv.data_ptr()
-        return nrefs, pr
+                    need[(r, name)] = self._check_out(result[(r, name)], m >> 1)
+        return nrefs, _poc_result(need)
 
     def _check_bi(self, bi: dict, preds: int):
         """vame_bipred's arrays of the alignments in `preds`: two 2-pointer arrays."""
@@ -463,15 +479,7 @@ class Engine:
         cur = self._frame(cur)
         n = cus.shape[0]
         self._check_scalar(count, "count")
-        if out is None:
-            out = torch.empty_like(cus)
-        else:
-            self._check_cus(out, 20, "out", n)
-        if cost is None:
-            cost = torch.empty(n, dtype=torch.int64, device=self.device)
-        elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
-              or not cost.is_contiguous()):
-            raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
+        out, cost = self._refine_out(cus, out, cost)
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
         check(lib().vame_bipred_refine(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(count),
                                        float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
@@ -642,15 +650,7 @@ class Engine:
         cur = self._frame(cur)
         n = cus.shape[0]
         self._check_scalar(ncus, "ncus")
-        if out is None:
-            out = torch.empty_like(cus)
-        else:
-            self._check_cus(out, 12, "out", n)
-        if cost is None:
-            cost = torch.empty(n, dtype=torch.int64, device=self.device)
-        elif (cost.dtype != torch.int64 or cost.numel() != n or cost.device != self.device
-              or not cost.is_contiguous()):
-            raise ValueError(f"cost must be a contiguous int64 [{n}] tensor on {self.device}")
+        out, cost = self._refine_out(cus, out, cost)
         bad = torch.zeros((), dtype=torch.int32, device=self.device)
         check(lib().vame_affine_search(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(ncus), float(lam),
                                        int(extra), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
@@ -698,11 +698,7 @@ class Engine:
         refs = [self._frame(r) for r in refs]
         out = out if out is not None else self.alloc_poc(len(refs), modes)
         self._check_poc_out(out, len(refs), modes)
-        pr = PocResult()
-        for (r, name), (cost, cpmv) in out.items():
-            m = MODES.index(name)
-            pr.cost[r][m] = cost.data_ptr()
-            pr.cpmvs[r][m] = cpmv.data_ptr()
+        pr = _poc_result(out)
         ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
         check(lib().vame_affine_me_poc(self._h, _ptr(cur), ref_ptrs, len(refs), float(lam), modes,
                                        extra, ctypes.byref(pr), self._stream()))

@@ -38,6 +38,7 @@ UNITS := engine=vame_engine.hip=KFLAGS 2cp=vame_kernels_2cp.hip=KFLAGS_2CP stage
          pack=vame_pack.hip=KFLAGS templates=vame_templates.cpp mc=vame_mc.hip \
          partition=vame_partition.hip bipred=vame_bipred.hip birefine=vame_birefine.hip \
          seed=vame_seed.hip search=vame_search.hip \
+         birefine_p=vame_birefine_p.hip search_p=vame_search_p.hip \
          hostlogic=vame_hostlogic.cpp io=vame_io.cpp
 unit_tag   = $(word 1,$(subst =, ,$(1)))
 unit_src   = $(CSRC)/$(word 2,$(subst =, ,$(1)))

@@ -447,6 +447,114 @@ int vame_affine_me_seeded(vame_ctx* ctx, const uint16_t* cur, const uint16_t* co
                           vame_mv* const seed_mv[4][2], const vame_poc_result* res /* in-out */,
                           void* work, size_t work_bytes, int32_t* bad, void* stream);
 
+/* ---- Rates against a motion-vector predictor.  Every rate
+ * above prices CPMVs against the all-zero predictor, the only one the
+ * reference's callers pass (affine.cl:431-434); its rate function takes any
+ * (calc_affine_bits, aux_functions.cl:2140-2189).  These calls expose it.  For
+ * CPMVs c, a predictor P (LT, RT, LB) and n control points, with q = the
+ * search's 1/16 -> 1/4 pel rounding and eg = its Exp-Golomb length:
+ *   bits_p(c, P, n) = eg(q(c.LT.x) - q(P.LT.x)) + eg(q(c.LT.y) - q(P.LT.y))
+ *                   + eg(q(c.RT.x) - q(P.RT.x + c.LT.x - P.LT.x)) + the same in y
+ *                   + (n == 3) * [eg(q(c.LB.x) - q(P.LB.x + c.LT.x - P.LT.x)) + the same in y]
+ * bits_p(c, 0, n) is the search's bits of c.  The rate term is floor(lambda *
+ * (bits_p + 2)); a bi CU pays floor(lambda * (both hypotheses' bits_p + 4)).
+ * Predictor components lie in [-2^17, 2^17 - 1].  The fused search
+ * (vame_affine_me*) and the seed searches keep the zero predictor.
+ *
+ * Descriptor-list calls take `preds`, device memory: a general affine
+ * predictor per hypothesis, nCPs ignored, all six components checked -- one
+ * entry per vame_mc_cu, two per vame_mc_bicu (hypothesis h of descriptor i at
+ * 2i + h; the second is not read when ref1 < 0).  preds == NULL is the zero
+ * predictor: the call's outputs are then bit for bit its counterpart's.  A
+ * predictor component out of range makes its descriptor invalid, with what
+ * the counterpart does for an invalid descriptor.  Each call keeps every other
+ * guarantee of its counterpart word for word: nothing read on the host,
+ * allocated or synchronized; `stream` alone, capturable; the device-side
+ * count; VAME_E_UNSUPPORTED under PROF; argument errors write nothing. */
+
+/* vame_affine_mc_bi with bits_p in the cost.  The samples do not depend on the
+ * predictor.  A uni descriptor (ref1 == -1) is the uni case: its cost is the
+ * SATD + floor(lambda * (bits_p(cp0, preds[2i]) + 2)). */
+int vame_affine_mc_bi_p(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                        const vame_mc_bicu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                        float lambda, uint16_t* pred, int64_t* cost, int32_t* bad, void* stream);
+
+/* vame_affine_search with bits_p(., preds[i]) in every iteration's cost, so
+ * the predictor takes part in which iteration wins.  cost[i] is bit for bit
+ * vame_affine_mc_bi_p's cost of out[i] (as a uni descriptor) with preds[i]. */
+int vame_affine_search_p(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                         const vame_mc_cu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                         float lambda, int extra_grad_iter, vame_mc_cu* out, int64_t* cost, int32_t* bad,
+                         void* stream);
+
+/* vame_bipred_refine with bits_p(., preds[2i + h]) for hypothesis h, in the
+ * start cost and in every comparison.  The cost never rises; cost[i] is bit
+ * for bit vame_affine_mc_bi_p's cost of out[i] with the same predictors. */
+int vame_bipred_refine_p(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                         const vame_mc_bicu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                         float lambda, int rounds, vame_mc_bicu* out, int64_t* cost, int32_t* bad, void* stream);
+
+/* Row-layout calls take translational predictors in the seed layout, so the mv
+ * arrays of a vame_seed_result can be passed as they are: the predictor of a
+ * row is LT = RT = LB = mv[r][alignment][row].  An array of an (r, alignment)
+ * the call uses must not be NULL (VAME_E_INVALID, nothing written). */
+typedef struct { const vame_mv* mv[4][2]; } vame_mvp;   /* [ref][align], nCtus*{201|284} rows */
+
+/* Re-price a POC's search results: for every r < nrefs, every PRED m in
+ * pred_mask and every row whose CU lies wholly in the frame,
+ *   cost <- cost - floor(lambda * (bits(cp) + 2)) + floor(lambda * (bits_p(cp, P, n) + 2)),
+ * n = 2 + (m & 1), cp the row's CPMVs, P its predictor.  CPMVs and all other
+ * rows are untouched; a row whose predictor is out of range is skipped and ORs
+ * 1 into *bad.  res must hold zero-predictor costs of the same lambda (what the
+ * fused search wrote): the call cannot tell, and a second call prices twice.
+ * The new cost equals vame_affine_mc_bi_p's cost of the row's CPMVs with that
+ * predictor; it is pure arithmetic, no prediction is made.  PROF does not
+ * enter.  Reads nothing on the host, allocates and synchronizes nothing, runs
+ * on `stream` alone and can be captured.  Argument errors (NULL ctx, mvp, res
+ * or bad; nrefs outside 1..4; an empty or unknown mask; a NULL array of a PRED
+ * or of an (r, alignment) in the mask): VAME_E_INVALID, nothing written. */
+int vame_reprice(vame_ctx* ctx, int nrefs, float lambda, int pred_mask, const vame_mvp* mvp,
+                 const vame_poc_result* res /* in-out, costs only */, int32_t* bad, void* stream);
+
+/* vame_affine_me_seeded's rule with d2 and d3 run by vame_affine_search_p's
+ * rule under the row's predictor (the 3-CP start still comes from
+ * affine.cl:81-105).  res is expected re-priced under the same mvp
+ * (vame_reprice); the merge is strict <.  A row whose predictor is out of
+ * range is skipped and ORs 1 into *bad, as one whose seed is.  With an
+ * all-zero mvp the call equals vame_affine_me_seeded bit for bit.  work: at
+ * least vame_seeded_p_work_bytes (the seeded call's lists and one predictor
+ * per slot). */
+size_t vame_seeded_p_work_bytes(vame_ctx* ctx, int nrefs, int mode_mask);
+int vame_affine_me_seeded_p(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                            float lambda, int mode_mask, int extra_grad_iter, vame_mv* const seed_mv[4][2],
+                            const vame_mvp* mvp, const vame_poc_result* res /* in-out */, void* work,
+                            size_t work_bytes, int32_t* bad, void* stream);
+
+/* vame_bipred's rule; only the bi cost changes.  The hypothesis of refIdx r is
+ * still the first minimum of the given costs (which the caller has re-priced);
+ * the bi cost is the SATD of the bi block + floor(lambda * (bits_p(cp0, P[r0])
+ * + bits_p(cp1, P[r1]) + 4)), P[r] the row's predictor of refIdx r.  There is
+ * no bad flag: a row with a predictor out of range, of any r < nrefs, keeps
+ * INT64_MAX and -1. */
+int vame_bipred_p(vame_ctx* ctx, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                  const vame_poc_result* res, int pred_mask, const vame_mvp* mvp, int64_t* const bi_cost[2],
+                  int32_t* const bi_sel[2], void* stream);
+
+/* The predictors of a descriptor list, for vame_bipred_refine_p and
+ * vame_affine_mc_bi_p on vame_partition_bi's leaves without a host read.  For
+ * each of the first min(*ncus_dev, max_cus) descriptors (ncus_dev NULL:
+ * max_cus) and each hypothesis h: if (x mod 128, y mod 128, w, h) is a
+ * candidate per vame_partition_table, in a CTU of the frame, preds[2i + h] is
+ * the mvp row of (ref_h, its alignment, ctu*{201|284} + offset) expanded to LT
+ * = RT = LB; otherwise -- no candidate, ref_h outside 0..3 (a uni descriptor's
+ * ref1), or a NULL array -- zero.  Both entries of a descriptor are written.
+ * Nothing is validated here: the consuming call checks the ranges.  Reads
+ * nothing on the host, allocates and synchronizes nothing, `stream` alone,
+ * capturable.  Argument errors (NULL ctx, mvp, cus or preds; max_cus outside
+ * 0..VAME_MC_MAX_CUS): VAME_E_INVALID, nothing written. */
+int vame_mvp_gather(vame_ctx* ctx, const vame_mvp* mvp, const vame_mc_bicu* cus, int max_cus,
+                    const int32_t* ncus_dev, vame_cpmvs* preds, void* stream);
+
 /* PROF (prediction refinement with optical flow).  The reference carries the
  * code but hard-disables it (`int enablePROF=0`, affine.cl:168 / :1132;
  * aux_functions.cl:215-605, :1096-1239); enable != 0 turns it on for the

@@ -28,4 +28,12 @@ struct BiRowsParams {
 // The launches of one vame_bipred call on `stream`.
 hipError_t bipred_launch(const BiRowsParams& p, hipStream_t stream);
 
+// vame_bipred_p: the rows' translational predictors in the seed
+// layout.  Only the closing kernel reads them (the pair SATDs do not depend on
+// a predictor): it is an instance of its own.
+struct BiRowsParamsP : BiRowsParams {
+  const int32_t* mvp[4][2];  // vame_mv [rows], [refIdx][align]
+};
+hipError_t bipred_p_launch(const BiRowsParamsP& p, hipStream_t stream);
+
 }  // namespace vame

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "vame_bipred.h"
 
@@ -34,7 +35,10 @@ constexpr int kBiThreads = 256;  // vame_bipred's workgroups
 constexpr long long kBiInf = 0x7fffffffffffffffll;
 static_assert(sizeof(BiCand) == 16, "one 16-byte load");
 
-__global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McBiParams p) {
+// MVP: vame_affine_mc_bi_p, the rate against the descriptor's predictors
+// (affine_bits_p); the samples do not depend on them.
+template <bool MVP>
+__global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McParamsT<McBiCu, MVP> p) {
   __shared__ uint4 s_coef[48];
   const int tid = threadIdx.x;
   if (tid < 48) s_coef[tid] = reinterpret_cast<const uint4*>(&kCoefTab)[tid];
@@ -64,14 +68,14 @@ __global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McBiParams p)
     int acc[4][4];
     mc_hyp_acc(ref0, cu.x, cu.y, lw, lh, cp0, cu.ncps0, sx, sy, W, H, s_coef, acc);
     uint2 P[4];
-    int bits = affine_bits(cp0, cu.ncps0) + kRuiBits;
+    int bits = MVP ? 0 : affine_bits(cp0, cu.ncps0) + kRuiBits;  // MVP: by the CU's first lane, below
     if (cu.ref1 >= 0) {
       const uint16_t* __restrict__ ref1 =
           cu.ref1 == 0 ? p.refs[0] : cu.ref1 == 1 ? p.refs[1] : cu.ref1 == 2 ? p.refs[2] : p.refs[3];
       int acc1[4][4];
       mc_hyp_acc(ref1, cu.x, cu.y, lw, lh, cp1, cu.ncps1, sx, sy, W, H, s_coef, acc1);
       mc_bi_pack(acc, acc1, P);
-      bits += affine_bits(cp1, cu.ncps1) + kRuiBits;
+      if constexpr (!MVP) bits += affine_bits(cp1, cu.ncps1) + kRuiBits;
     } else {
       mc_bi_pack(acc, acc, P);  // (2 * acc) >> 11 == acc >> 10
     }
@@ -90,6 +94,17 @@ __global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McBiParams p)
       for (int r = 0; r < 4; r++) O[r] = *reinterpret_cast<const uint2*>(base + (b0 + r * bw));
       long long v = row_sum16(satd_4x4(O, P));
       // the CU's first lane adds the rate: each hypothesis with its own ruiBits
+      if constexpr (MVP) {
+        if (local == 0) {  // against the hypotheses' predictors, read by this lane alone
+          MvPred<true> pp;
+          pp.load(p.preds + (size_t)lo * 2 * kMvpWords);
+          bits = pp.bits(cp0, cu.ncps0) + kRuiBits;
+          if (cu.ref1 >= 0) {
+            pp.load(p.preds + ((size_t)lo * 2 + 1) * kMvpWords);
+            bits += pp.bits(cp1, cu.ncps1) + kRuiBits;
+          }
+        }
+      }
       if (local == 0) v += mc_rate(p.lambda, bits);
       if ((local & 15) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(p.cost + lo), (unsigned long long)v);
     }
@@ -97,7 +112,10 @@ __global__ __launch_bounds__(kMcThreads) void mc_bi_predict_kernel(McBiParams p)
 }
 
 hipError_t mc_bi_launch(const McBiParams& p, hipStream_t stream) {
-  return mc_launch_concat(p, mc_bi_predict_kernel, stream);
+  return mc_launch_concat(p, mc_bi_predict_kernel<false>, stream);
+}
+hipError_t mc_bi_p_launch(const McBiParamsP& p, hipStream_t stream) {
+  return mc_launch_concat(p, mc_bi_predict_kernel<true>, stream);
 }
 
 // ------------------------------------------------------------------ vame_bipred
@@ -196,24 +214,37 @@ __global__ __launch_bounds__(kBiThreads) void bipred_rows_kernel(BiRowsParams p)
   }
 }
 
-template <int R>
-__device__ __forceinline__ void bi_rate(const BiRowsParams& p, int align, int row, int& m, int& bits) {
+// PT = BiRowsParamsP: the rate against the row's predictor of refIdx R (its mvp
+// entry, LT = RT = LB); false when that predictor is out of range.
+template <int R, class PT>
+__device__ __forceinline__ bool bi_rate(const PT& p, int align, int row, int& m, int& bits) {
   m = bi_model<R>(p, align, row);
   int cp[6];
   bi_load_cp<R>(p, align, m, row, cp);
-  bits = affine_bits(cp, 2 + m) + kRuiBits;
+  if constexpr (std::is_same<PT, BiRowsParamsP>::value) {
+    const int32_t* mvp = align ? p.mvp[R][1] : p.mvp[R][0];
+    const int qx = mvp[2 * (size_t)row], qy = mvp[2 * (size_t)row + 1];
+    if (!mc_mv_ok(qx) || !mc_mv_ok(qy)) return false;
+    const int P[6] = {qx, qy, qx, qy, qx, qy};
+    bits = affine_bits_p(cp, P, 2 + m) + kRuiBits;
+  } else {
+    bits = affine_bits(cp, 2 + m) + kRuiBits;
+  }
+  return true;
 }
 
-__global__ __launch_bounds__(kBiThreads) void bipred_close_kernel(BiRowsParams p) {
+template <class PT>
+__global__ __launch_bounds__(kBiThreads) void bipred_close_kernel(PT p) {
   const int cand = p.candBegin + blockIdx.x * kBiThreads + threadIdx.x;
   if (cand >= p.candEnd) return;
   const BiCand cd = p.cands[cand];
   const int align = (cd.shape >> 8) & 1, row = cd.row;
   int m[4] = {0, 0, 0, 0}, bits[4] = {0, 0, 0, 0};
-  bi_rate<0>(p, align, row, m[0], bits[0]);
-  bi_rate<1>(p, align, row, m[1], bits[1]);
-  if (p.nrefs > 2) bi_rate<2>(p, align, row, m[2], bits[2]);
-  if (p.nrefs > 3) bi_rate<3>(p, align, row, m[3], bits[3]);
+  bool ok = bi_rate<0>(p, align, row, m[0], bits[0]);
+  ok = bi_rate<1>(p, align, row, m[1], bits[1]) && ok;
+  if (p.nrefs > 2) ok = bi_rate<2>(p, align, row, m[2], bits[2]) && ok;
+  if (p.nrefs > 3) ok = bi_rate<3>(p, align, row, m[3], bits[3]) && ok;
+  if (!ok) return;  // vame_bipred_p: a row with a predictor out of range keeps INT64_MAX / -1
   long long best = kBiInf;
   int sel = -1;
   int pair = 0;
@@ -232,17 +263,22 @@ __global__ __launch_bounds__(kBiThreads) void bipred_close_kernel(BiRowsParams p
   p.biSel[align][row] = sel;
 }
 
-hipError_t bipred_launch(const BiRowsParams& p, hipStream_t stream) {
+template <class PT>
+static hipError_t bipred_launch_t(const PT& p, hipStream_t stream) {
   const int nCand = p.candEnd - p.candBegin, nGroups = p.groupEnd - p.groupBegin;
   const int nInit = std::max(std::max(p.biCost[0] ? p.rowsOf[0] : 0, p.biCost[1] ? p.rowsOf[1] : 0), nCand * kBiPairs);
   if (nInit > 0)
-    hipLaunchKernelGGL(bipred_init_kernel, dim3((nInit + kBiThreads - 1) / kBiThreads), dim3(kBiThreads), 0, stream, p);
+    hipLaunchKernelGGL(bipred_init_kernel, dim3((nInit + kBiThreads - 1) / kBiThreads), dim3(kBiThreads), 0, stream,
+                       static_cast<const BiRowsParams&>(p));
   if (p.nrefs >= 2 && nCand > 0) {
     hipLaunchKernelGGL(bipred_rows_kernel, dim3((nGroups + kBiThreads / 16 - 1) / (kBiThreads / 16)), dim3(kBiThreads),
-                       0, stream, p);
-    hipLaunchKernelGGL(bipred_close_kernel, dim3((nCand + kBiThreads - 1) / kBiThreads), dim3(kBiThreads), 0, stream, p);
+                       0, stream, static_cast<const BiRowsParams&>(p));
+    hipLaunchKernelGGL(bipred_close_kernel<PT>, dim3((nCand + kBiThreads - 1) / kBiThreads), dim3(kBiThreads), 0, stream,
+                       p);
   }
   return hipGetLastError();
 }
+hipError_t bipred_launch(const BiRowsParams& p, hipStream_t stream) { return bipred_launch_t(p, stream); }
+hipError_t bipred_p_launch(const BiRowsParamsP& p, hipStream_t stream) { return bipred_launch_t(p, stream); }
 
 }  // namespace vame

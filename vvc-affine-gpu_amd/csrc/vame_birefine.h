@@ -21,4 +21,12 @@ struct BiRefineParams {
 // per size class, no scratch.
 hipError_t birefine_launch(const BiRefineParams& p, hipStream_t stream);
 
+// vame_bipred_refine_p: the same block and the predictors; its
+// kernels are instances of their own, vame_bipred_refine's hold no predictor
+// code.
+struct BiRefineParamsP : BiRefineParams {
+  const int32_t* preds;  // vame_cpmvs (7 int32): hypothesis h of descriptor i at 2i + h
+};
+hipError_t birefine_p_launch(const BiRefineParamsP& p, hipStream_t stream);
+
 }  // namespace vame

@@ -98,6 +98,37 @@ __device__ __forceinline__ int affine_bits(const int* c, int ncp) {
   return b;
 }
 
+// aux_functions.cl:2140-2189 against the predictor P (LT, RT, LB as c; QUARTER
+// precision, cost_scale 0, imvShift 0): LT against P's LT, RT and LB against
+// P's moved by the LT difference.  Components of c and P within [kMvMin,
+// kMvMax]: the composed predictor stays within 3 * 2^17.  P = 0 gives
+// affine_bits(c, ncp).
+__device__ __forceinline__ int affine_bits_p(const int* c, const int* P, int ncp) {
+  const int dx = c[0] - P[0], dy = c[1] - P[1];
+  int b = eg_bits(to_quarter(c[0]) - to_quarter(P[0])) + eg_bits(to_quarter(c[1]) - to_quarter(P[1])) +
+          eg_bits(to_quarter(c[2]) - to_quarter(P[2] + dx)) + eg_bits(to_quarter(c[3]) - to_quarter(P[3] + dy));
+  if (ncp == 3) b += eg_bits(to_quarter(c[4]) - to_quarter(P[4] + dx)) + eg_bits(to_quarter(c[5]) - to_quarter(P[5] + dy));
+  return b;
+}
+// The predictor of a rate site: in the kernels of the calls without predictors
+// (MVP = false) an empty object whose bits() is affine_bits -- those kernels
+// hold no predictor code or state; with MVP the six components, loaded from a
+// vame_cpmvs (7 int32: nCPs, ignored, then LT, RT, LB), and affine_bits_p.
+template <bool MVP>
+struct MvPred {
+  __device__ __forceinline__ void load(const int32_t*) {}
+  __device__ __forceinline__ int bits(const int* c, int ncp) const { return affine_bits(c, ncp); }
+};
+template <>
+struct MvPred<true> {
+  int p[6];
+  __device__ __forceinline__ void load(const int32_t* P) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) p[k] = P[1 + k];
+  }
+  __device__ __forceinline__ int bits(const int* c, int ncp) const { return affine_bits_p(c, p, ncp); }
+};
+
 // (int)double with the semantics the reference's kernels get from the GPU:
 // truncation, NaN -> 0, out-of-range values saturate -- exactly what
 // v_cvt_i32_f64 does, so it is issued directly (a C++ cast of an out-of-range

@@ -50,8 +50,11 @@ constexpr int kMcMaxBlocks = 2048;  // prediction grid (grid-strided beyond it)
 static_assert(kMcMaxCus <= kMcScanBlock * kMcScanBlock, "two scan levels");
 
 // The parameter block of vame_affine_mc (Cu = McCu) and vame_affine_mc_bi
-// (Cu = McBiCu).
-template <class Cu>
+// (Cu = McBiCu); MVP: of vame_affine_mc_bi_p, the same block and the predictors
+// (DESIGN.md §17).  The kernels of the calls without predictors are the MVP =
+// false instances: they take the block they always took and hold no predictor
+// code.
+template <class Cu, bool MVP = false>
 struct McParamsT {
   const uint16_t* cur;      // NULL when cost is
   const uint16_t* refs[4];
@@ -67,12 +70,18 @@ struct McParamsT {
   // clamped to [0, ncus] (ncus sizes the grids); NULL: the count is ncus
   const int32_t* ncusDev;
 };
+template <class Cu>
+struct McParamsT<Cu, true> : McParamsT<Cu, false> {
+  const int32_t* preds;  // vame_cpmvs (7 int32), two per bi descriptor: hypothesis h of descriptor i at 2i + h
+};
 using McParams = McParamsT<McCu>;
 using McBiParams = McParamsT<McBiCu>;
+using McBiParamsP = McParamsT<McBiCu, true>;
 // The three launches of one vame_affine_mc / vame_affine_mc_bi call on
 // `stream` (ncus >= 1).
 hipError_t mc_launch(const McParams& p, bool prof, hipStream_t stream);
 hipError_t mc_bi_launch(const McBiParams& p, hipStream_t stream);
+hipError_t mc_bi_p_launch(const McBiParamsP& p, hipStream_t stream);
 
 // ------------------------------------------------------------------- validity
 __device__ __forceinline__ bool mc_size_ok(int v) { return v == 16 || v == 32 || v == 64 || v == 128; }
@@ -99,6 +108,27 @@ __device__ __forceinline__ bool mc_cu_ok(const McBiCu& cu, int W, int H, int nre
   ok = ok && cu.ref1 >= -1 && cu.ref1 < nrefs;
   if (cu.ref1 >= 0) ok = ok && mc_cp_ok(cu.ncps1, cu.c1);
   return ok;
+}
+
+// --------------------------------------------------------------- predictors
+// A predictor (vame_cpmvs: nCPs, which is ignored, then LT, RT, LB) is valid
+// when all six components lie within [kMvMin, kMvMax], whatever the model of
+// the hypothesis it prices; an invalid one makes its descriptor invalid.
+constexpr int kMvpWords = 7;
+__device__ __forceinline__ bool mvp_ok(const int32_t* P) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 1; k < kMvpWords; k++) ok = ok && mc_mv_ok(P[k]);
+  return ok;
+}
+// The predictors of descriptor i: one for a uni descriptor (McCu), two for a
+// bi descriptor, the second not read when ref1 < 0.
+__device__ __forceinline__ bool mvp_cu_ok(const McCu&, const int32_t* preds, int i) {
+  return mvp_ok(preds + (size_t)i * kMvpWords);
+}
+__device__ __forceinline__ bool mvp_cu_ok(const McBiCu& cu, const int32_t* preds, int i) {
+  const int32_t* P = preds + (size_t)i * 2 * kMvpWords;
+  return mvp_ok(P) && (cu.ref1 < 0 || mvp_ok(P + kMvpWords));
 }
 
 // ------------------------------------------------- sub-block concatenation
@@ -132,8 +162,8 @@ __device__ __forceinline__ int block_scan_1024(int v, int* s_wave, int& total) {
 
 // Validate each descriptor, count its sub-blocks (0 for an invalid one), zero
 // its cost, flag `bad`; exclusive scan of the counts inside the scan block.
-template <class Cu>
-__global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParamsT<Cu> p) {
+template <class Cu, bool MVP = false>
+__global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParamsT<Cu, MVP> p) {
   __shared__ int s_wave[kMcScanBlock / 64];
   const int i = blockIdx.x * kMcScanBlock + threadIdx.x;
   const int ncus = mc_ncus(p.ncusDev, p.ncus);
@@ -141,7 +171,8 @@ __global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParamsT<Cu> p)
   bool flag = false;
   if (i < ncus) {
     const Cu cu = p.cus[i];
-    const bool ok = mc_cu_ok(cu, p.W, p.H, p.nrefs);
+    bool ok = mc_cu_ok(cu, p.W, p.H, p.nrefs);
+    if constexpr (MVP) ok = ok && mvp_cu_ok(cu, p.preds, i);
     n = ok ? (cu.w * cu.h) >> 4 : 0;
     flag = !ok;
     if (p.cost) p.cost[i] = 0;
@@ -158,8 +189,8 @@ __global__ __launch_bounds__(kMcScanBlock) void mc_count_kernel(McParamsT<Cu> p)
 // one per thread, summed by the workgroup); the last block writes the total.
 // It reads no descriptor: Cu only names the call's parameter block, so that the
 // kernel keeps the arguments it had (two identical instantiations, one per unit).
-template <class Cu>
-__global__ __launch_bounds__(kMcScanBlock) void mc_offsets_kernel(McParamsT<Cu> p) {
+template <class Cu, bool MVP = false>
+__global__ __launch_bounds__(kMcScanBlock) void mc_offsets_kernel(McParamsT<Cu, MVP> p) {
   __shared__ int s_wave[kMcScanBlock / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int ncus = mc_ncus(p.ncusDev, p.ncus);
@@ -173,11 +204,11 @@ __global__ __launch_bounds__(kMcScanBlock) void mc_offsets_kernel(McParamsT<Cu> 
 
 // Count, offsets and `predict` (the unit's kernel, grid-strided over the
 // concatenation) on `stream`.
-template <class Cu>
-hipError_t mc_launch_concat(const McParamsT<Cu>& p, void (*predict)(McParamsT<Cu>), hipStream_t stream) {
+template <class Cu, bool MVP>
+hipError_t mc_launch_concat(const McParamsT<Cu, MVP>& p, void (*predict)(McParamsT<Cu, MVP>), hipStream_t stream) {
   const int nb = (p.ncus + kMcScanBlock - 1) / kMcScanBlock;
-  hipLaunchKernelGGL(mc_count_kernel<Cu>, dim3(nb), dim3(kMcScanBlock), 0, stream, p);
-  hipLaunchKernelGGL(mc_offsets_kernel<Cu>, dim3(nb), dim3(kMcScanBlock), 0, stream, p);
+  hipLaunchKernelGGL((mc_count_kernel<Cu, MVP>), dim3(nb), dim3(kMcScanBlock), 0, stream, p);
+  hipLaunchKernelGGL((mc_offsets_kernel<Cu, MVP>), dim3(nb), dim3(kMcScanBlock), 0, stream, p);
   // at most 1024 sub-blocks per descriptor: 4 workgroups
   const int grid = (int)std::min<long long>(4ll * p.ncus, kMcMaxBlocks);
   hipLaunchKernelGGL(predict, dim3(grid), dim3(kMcThreads), 0, stream, p);

@@ -37,4 +37,16 @@ struct PartParams {
 // vame_partition_bi call (the leaf may be a bi-predicted one).
 hipError_t partition_launch(const PartParams& p, hipStream_t stream, bool bi = false);
 
+// vame_mvp_gather: per bi descriptor and hypothesis the
+// predictor of the candidate row the descriptor's rectangle is, or zero.
+struct McBiCu;
+struct MvpGatherParams {
+  const int32_t* mvp[4][2];  // vame_mv [rows], [refIdx][align]; NULL: that array is not given
+  const McBiCu* cus;
+  int32_t* preds;            // vame_cpmvs (7 int32), two per descriptor
+  const int32_t* ncusDev;    // or NULL: the count is maxCus
+  int maxCus, ctusPerRow, nCtus;
+};
+hipError_t mvp_gather_launch(const MvpGatherParams& p, hipStream_t stream);
+
 }  // namespace vame

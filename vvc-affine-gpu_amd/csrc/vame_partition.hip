@@ -339,6 +339,49 @@ hipError_t partition_launch(const PartParams& p, hipStream_t stream, bool bi) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------- vame_mvp_gather
+// One lane per bi descriptor: a rectangle that is a candidate CU of its CTU
+// (kPartTable) takes, per hypothesis, the predictor of its row in the arrays of
+// (ref, alignment), expanded to LT = RT = LB; anything else -- no candidate,
+// outside the CTU grid, a reference without an array -- the zero predictor.
+// The second entry is written for uni descriptors too (zero).
+__global__ __launch_bounds__(kPartThreads) void mvp_gather_kernel(MvpGatherParams p) {
+  const int i = blockIdx.x * kPartThreads + threadIdx.x;
+  if (i >= mc_ncus(p.ncusDev, p.maxCus)) return;
+  const McBiCu cu = p.cus[i];
+  int align = -1, row = 0;
+  if (mc_size_ok(cu.w) && mc_size_ok(cu.h) && cu.x >= 0 && cu.y >= 0 && ((cu.x | cu.y) & 15) == 0 &&
+      (cu.x >> 7) < p.ctusPerRow) {
+    const int ctu = (cu.y >> 7) * p.ctusPerRow + (cu.x >> 7);
+    const int e = kPartTable.v[part_slot(part_log16(cu.w), part_log16(cu.h), (cu.y & 127) >> 4, (cu.x & 127) >> 4)];
+    if (ctu < p.nCtus && e >= 0) {
+      align = e >> 9;
+      row = ctu * (align ? kHalfCusPerCtu : kFullCusPerCtu) + (e & 511);
+    }
+  }
+  const int refs[2] = {cu.ref0, cu.ref1};
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int32_t* mvp = nullptr;
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+      for (int aa = 0; aa < 2; aa++)
+        if (rr == refs[h] && aa == align) mvp = p.mvp[rr][aa];
+    const int qx = mvp ? mvp[2 * (size_t)row] : 0, qy = mvp ? mvp[2 * (size_t)row + 1] : 0;
+    int32_t* P = p.preds + ((size_t)i * 2 + h) * kMvpWords;
+    P[0] = 3;
+    P[1] = P[3] = P[5] = qx;
+    P[2] = P[4] = P[6] = qy;
+  }
+}
+
+hipError_t mvp_gather_launch(const MvpGatherParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(mvp_gather_kernel, dim3((p.maxCus + kPartThreads - 1) / kPartThreads), dim3(kPartThreads), 0, stream,
+                     p);
+  return hipGetLastError();
+}
+
 }  // namespace vame
 
 extern "C" int vame_partition_table(int32_t* table) {

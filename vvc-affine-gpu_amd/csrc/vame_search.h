@@ -22,6 +22,14 @@ struct SearchParams {
 // per size class, no scratch.
 hipError_t search_launch(const SearchParams& p, hipStream_t stream);
 
+// vame_affine_search_p: the same block and one predictor per
+// descriptor; its kernels are instances of their own, vame_affine_search's hold
+// no predictor code.
+struct SearchParamsP : SearchParams {
+  const int32_t* preds;  // vame_cpmvs (7 int32) [maxCus]
+};
+hipError_t search_p_launch(const SearchParamsP& p, hipStream_t stream);
+
 // vame_affine_me_seeded's work buffer: the count of seeded rows, then per slot
 // (capacity = refs x in-frame candidates of the alignments in the mask) the
 // 2-CP descriptor, its cost, where it goes (refIdx | align << 2, row) and, with
@@ -68,5 +76,32 @@ struct SeededParams {
 };
 // The launches of one vame_affine_me_seeded call on `stream`.
 hipError_t seeded_launch(const SeededParams& p, hipStream_t stream);
+
+// vame_affine_me_seeded_p: the rows' translational predictors
+// in the seed layout; the build kernel expands a row's to LT = RT = LB in
+// `preds` (the work buffer's tail, one vame_cpmvs per slot), which both
+// searches price against.
+struct SeededParamsP : SeededParams {
+  const int32_t* mvp[4][2];  // vame_mv [rows], [refIdx][align]
+  int32_t* preds;            // [cap][7]
+};
+inline size_t seeded_p_work_bytes(size_t cap, bool with3) {
+  return seeded_work_bytes(cap, with3) + cap * 7 * sizeof(int32_t);
+}
+hipError_t seeded_p_launch(const SeededParamsP& p, hipStream_t stream);
+
+// vame_reprice: the zero-predictor rate of every in-frame row's CPMVs replaced
+// by the rate against the row's predictor.
+struct RepriceParams {
+  const BiCand* cands;
+  int candBegin, candEnd;    // the in-frame candidates of the alignments in the mask
+  const int32_t* mvp[4][2];  // vame_mv [rows], [refIdx][align]
+  int64_t* cost[4][4];       // [refIdx][PRED]; NULL outside the mask
+  const int32_t* cpmv[4][4];
+  int32_t* bad;
+  int nrefs;
+  float lambda;
+};
+hipError_t reprice_launch(const RepriceParams& p, hipStream_t stream);
 
 }  // namespace vame

@@ -28,121 +28,16 @@
 //                         strictly lower
 #include <hip/hip_runtime.h>
 
-#include "vame_refine_core.h"
-#include "vame_search.h"
+#include <type_traits>
+
+#include "vame_search_kernel.h"
 
 namespace vame {
 
-template <int NT, int SB>
-__global__ __launch_bounds__(NT) void search_kernel(SearchParams p) {
-  __shared__ uint4 s_coef[48];
-  __shared__ uint2 s_pm[NT * SB * 4];  // P, int16 [h][w]: 16 samples per sub-block
-  __shared__ long long s_V[kNumMom];
-  __shared__ double s_M[42];
-  __shared__ unsigned long long s_sum;
-  const int tid = threadIdx.x, i = blockIdx.x;
-  if (i >= mc_ncus(p.ncusDev, p.maxCus)) return;
-  const McCu cu = p.cus[i];
-  const bool ok = mc_cu_ok(cu, p.W, p.H, p.nrefs);  // vame_affine_mc's validity rules
-  const int nsb = ok ? (cu.w * cu.h) >> 4 : 0;      // an invalid descriptor goes with the smallest class
-  if ((nsb <= 64 ? 64 : nsb <= 256 ? 256 : 1024) != NT * SB) return;
-  if (!ok) {
-    if (tid == 0) {
-      p.out[i] = cu;
-      p.cost[i] = 0;
-      atomicOr(p.bad, 1);
-    }
-    return;
-  }
-  if (tid < 48) s_coef[tid] = reinterpret_cast<const uint4*>(&kCoefTab)[tid];
-  __syncthreads();
-
-  const int W = p.W, H = p.H;
-  const int lw = 31 - __clz(cu.w), lh = 31 - __clz(cu.h);
-  const bool active = tid < nsb;          // the lane holds a sub-block
-  const int nq = SB == 1 ? 1 : nsb / NT;  // and, in a CU that fills the workgroup, nq of them (uniform)
-  const int sx0 = (tid & ((cu.w >> 2) - 1)) << 2, sy0 = (tid >> (lw - 2)) << 2;
-  const int syStep = (NT >> (lw - 2)) << 2;  // rows between a lane's sub-blocks
-  Geo g;
-  g.x = cu.x; g.y = cu.y; g.lw = lw; g.lh = lh; g.w = cu.w; g.h = cu.h;
-  const int ncp = cu.ncps;
-  int cc[6] = {cu.ltx, cu.lty, cu.rtx, cu.rty, cu.lbx, cu.lby};  // a 2-CP descriptor keeps its LB as given
-  int best[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) best[k] = cc[k];
-  const uint16_t* __restrict__ ref =
-      cu.ref == 0 ? p.refs[0] : cu.ref == 1 ? p.refs[1] : cu.ref == 2 ? p.refs[2] : p.refs[3];
-
-  uint2 O[SB][4] = {};
-  if (active) {
-    // x, sx are multiples of 4 and so is W: every row of a block is 8-byte aligned
-    const char* base = reinterpret_cast<const char*>(p.cur);
-    const size_t bw = (size_t)W * 2u;
-#pragma unroll
-    for (int q = 0; q < SB; q++) {
-      if (q >= nq) break;
-      const size_t b0 = ((size_t)(cu.y + sy0 + q * syStep) * W + cu.x + sx0) * 2u;
-#pragma unroll
-      for (int r = 0; r < 4; r++) O[q][r] = *reinterpret_cast<const uint2*>(base + (b0 + r * bw));
-    }
-  }
-
-  const int niter = (ncp == 3 ? 4 : 5) + p.extra;
-  long long bestCost = 0x7fffffffffffffffll;  // iteration 0's cost always replaces it
-#pragma unroll 1
-  for (int it = 0;; it++) {
-    // the lane's geometry is loop-invariant: hidden from the optimizer, or every
-    // address and monomial derived from it is hoisted and held across the loop
-    int sx = sx0, sy = sy0;
-    opaque(sx);
-    opaque(sy);
-    int s = 0;
-    if (active) {
-#pragma unroll
-      for (int q = 0; q < SB; q++) {
-        if (q >= nq) break;
-        const int syq = sy + q * syStep;
-        int acc[4][4];
-        mc_hyp_acc(ref, cu.x, cu.y, lw, lh, cc, ncp, sx, syq, W, H, s_coef, acc);
-        uint2 P[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          P[r] = make_uint2(pack16(clampi(acc[r][0] >> 10, 0, 1023), clampi(acc[r][1] >> 10, 0, 1023)),
-                            pack16(clampi(acc[r][2] >> 10, 0, 1023), clampi(acc[r][3] >> 10, 0, 1023)));
-        s += satd_4x4(O[q], P);
-        // P for the gradient step (unused after the last cost)
-#pragma unroll
-        for (int r = 0; r < 4; r++) s_pm[((syq + r) * cu.w + sx) >> 2] = P[r];
-      }
-    }
-    const long long cost = br_block_sum<NT>(s, &s_sum) + mc_rate(p.lambda, affine_bits(cc, ncp) + kRuiBits);
-    if (cost < bestCost) {
-      bestCost = cost;
-#pragma unroll
-      for (int k = 0; k < 6; k++) best[k] = cc[k];
-    }
-    if (it == niter) break;
-    // unchanged CPMVs repeat this iteration's prediction and cost: never strictly better
-    if (!br_step<NT, SB>(s_pm, O, s_V, s_M, g, ncp, active, nq, sx, sy, syStep, W, H, cc)) break;
-  }
-  if (tid == 0) {
-    McCu o = cu;
-    o.ltx = best[0]; o.lty = best[1]; o.rtx = best[2]; o.rty = best[3];
-    if (ncp == 3) {
-      o.lbx = best[4];
-      o.lby = best[5];
-    }
-    p.out[i] = o;
-    p.cost[i] = bestCost;
-  }
-}
-
-hipError_t search_launch(const SearchParams& p, hipStream_t stream) {
-  hipLaunchKernelGGL((search_kernel<64, 1>), dim3(p.maxCus), dim3(64), 0, stream, p);
-  hipLaunchKernelGGL((search_kernel<256, 1>), dim3(p.maxCus), dim3(256), 0, stream, p);
-  hipLaunchKernelGGL((search_kernel<512, 2>), dim3(p.maxCus), dim3(512), 0, stream, p);
-  return hipGetLastError();
-}
+hipError_t search_launch(const SearchParams& p, hipStream_t stream) { return search_launch_t(p, stream); }
+// the searches of the seeded calls: vame_affine_me_seeded_p's are vame_search_p.hip's
+static hipError_t seeded_search(const SearchParams& p, hipStream_t stream) { return search_launch(p, stream); }
+static hipError_t seeded_search(const SearchParamsP& p, hipStream_t stream) { return search_p_launch(p, stream); }
 
 // ------------------------------------------------------- vame_affine_me_seeded
 constexpr int kSeededThreads = 256;
@@ -151,7 +46,11 @@ __global__ __launch_bounds__(kSeededThreads) void seeded_zero_kernel(SeededParam
   if (threadIdx.x == 0) *p.work.count = 0;
 }
 
-__global__ __launch_bounds__(kSeededThreads) void seeded_build_kernel(SeededParams p) {
+// PT = SeededParamsP: the row's predictor (its mvp entry, LT = RT = LB) goes
+// with the descriptor; a row whose predictor is out of range is skipped.
+template <class PT>
+__global__ __launch_bounds__(kSeededThreads) void seeded_build_kernel(PT p) {
+  constexpr bool MVP = std::is_same<PT, SeededParamsP>::value;
   const int nc = p.candEnd - p.candBegin;
   const int t = blockIdx.x * kSeededThreads + threadIdx.x;
   if (t >= nc * p.search.nrefs) return;
@@ -170,7 +69,28 @@ __global__ __launch_bounds__(kSeededThreads) void seeded_build_kernel(SeededPara
     atomicOr(p.search.bad, 1);
     return;
   }
+  int qx = 0, qy = 0;
+  if constexpr (MVP) {
+    const int32_t* mvp = nullptr;
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+      for (int aa = 0; aa < 2; aa++)
+        if (rr == r && aa == align) mvp = p.mvp[rr][aa];
+    qx = mvp[2 * (size_t)cd.row];
+    qy = mvp[2 * (size_t)cd.row + 1];
+    if (!mc_mv_ok(qx) || !mc_mv_ok(qy)) {
+      atomicOr(p.search.bad, 1);
+      return;
+    }
+  }
   const int k = atomicAdd(p.work.count, 1);  // < cap: one slot per (refIdx, candidate)
+  if constexpr (MVP) {
+    int32_t* P = p.preds + (size_t)k * kMvpWords;
+    P[0] = 3;
+    P[1] = P[3] = P[5] = qx;
+    P[2] = P[4] = P[6] = qy;
+  }
   McCu cu;
   cu.x = cd.xy & 0xFFFF;
   cu.y = cd.xy >> 16;
@@ -230,27 +150,91 @@ __global__ __launch_bounds__(kSeededThreads) void seeded_merge_kernel(SeededPara
   if (p.with3) seeded_take(p, r, 2 * align + 1, row, p.work.cus3[k], p.work.cost3[k], 3);
 }
 
-hipError_t seeded_launch(const SeededParams& p, hipStream_t stream) {
+// The launches of vame_affine_me_seeded (PT = SeededParams, ST = SearchParams)
+// and of vame_affine_me_seeded_p (SeededParamsP, SearchParamsP): the zero, lb
+// and merge kernels take the base block in both.
+template <class PT, class ST>
+static hipError_t seeded_launch_t(const PT& p, ST s, hipStream_t stream) {
+  const SeededParams& base = p;
   const int n = p.cap;
-  hipLaunchKernelGGL(seeded_zero_kernel, dim3(1), dim3(kSeededThreads), 0, stream, p);
+  hipLaunchKernelGGL(seeded_zero_kernel, dim3(1), dim3(kSeededThreads), 0, stream, base);
   if (n == 0) return hipGetLastError();
   const dim3 grid((n + kSeededThreads - 1) / kSeededThreads), block(kSeededThreads);
-  hipLaunchKernelGGL(seeded_build_kernel, grid, block, 0, stream, p);
-  SearchParams s = p.search;
+  hipLaunchKernelGGL(seeded_build_kernel<PT>, grid, block, 0, stream, p);
   s.maxCus = n;
   s.ncusDev = p.work.count;
   s.cus = s.out = p.work.cus2;
   s.cost = p.work.cost2;
-  hipError_t e = search_launch(s, stream);
+  hipError_t e = seeded_search(s, stream);
   if (e != hipSuccess) return e;
   if (p.with3) {
-    hipLaunchKernelGGL(seeded_lb_kernel, grid, block, 0, stream, p);
+    hipLaunchKernelGGL(seeded_lb_kernel, grid, block, 0, stream, base);
     s.cus = s.out = p.work.cus3;
     s.cost = p.work.cost3;
-    e = search_launch(s, stream);
+    e = seeded_search(s, stream);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(seeded_merge_kernel, grid, block, 0, stream, p);
+  hipLaunchKernelGGL(seeded_merge_kernel, grid, block, 0, stream, base);
+  return hipGetLastError();
+}
+hipError_t seeded_launch(const SeededParams& p, hipStream_t stream) { return seeded_launch_t(p, p.search, stream); }
+hipError_t seeded_p_launch(const SeededParamsP& p, hipStream_t stream) {
+  SearchParamsP s;
+  static_cast<SearchParams&>(s) = p.search;
+  s.preds = p.preds;
+  return seeded_launch_t(p, s, stream);
+}
+
+// ---------------------------------------------------------------- vame_reprice
+// One lane per (refIdx, in-frame candidate): for each PRED of the candidate's
+// alignment in the mask, cost -= floor(lambda * (affine_bits + 2)), cost +=
+// floor(lambda * (affine_bits_p + 2)) with the row's predictor LT = RT = LB.
+// Pure arithmetic; a row whose predictor is out of range is skipped.
+__global__ __launch_bounds__(kSeededThreads) void reprice_kernel(RepriceParams p) {
+  const int nc = p.candEnd - p.candBegin;
+  const int t = blockIdx.x * kSeededThreads + threadIdx.x;
+  if (t >= nc * p.nrefs) return;
+  const int r = t / nc;
+  const BiCand cd = p.cands[p.candBegin + t - r * nc];
+  const int align = (cd.shape >> 8) & 1;
+  const int32_t* mvp = nullptr;
+  int64_t* c[2] = {nullptr, nullptr};
+  const int32_t* v[2] = {nullptr, nullptr};
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++)
+#pragma unroll
+    for (int aa = 0; aa < 2; aa++)
+      if (rr == r && aa == align) {
+        mvp = p.mvp[rr][aa];
+        c[0] = p.cost[rr][2 * aa];
+        c[1] = p.cost[rr][2 * aa + 1];
+        v[0] = p.cpmv[rr][2 * aa];
+        v[1] = p.cpmv[rr][2 * aa + 1];
+      }
+  if (!c[0] && !c[1]) return;  // no PRED of this alignment in the mask
+  const int qx = mvp[2 * (size_t)cd.row], qy = mvp[2 * (size_t)cd.row + 1];
+  if (!mc_mv_ok(qx) || !mc_mv_ok(qy)) {
+    atomicOr(p.bad, 1);
+    return;
+  }
+  const int P[6] = {qx, qy, qx, qy, qx, qy};
+#pragma unroll
+  for (int m = 0; m < 2; m++) {
+    if (!c[m]) continue;
+    const int32_t* a = v[m] + (size_t)cd.row * 7;
+    int cp[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) cp[k] = a[1 + k];
+    c[m][cd.row] += mc_rate(p.lambda, affine_bits_p(cp, P, 2 + m) + kRuiBits) -
+                    mc_rate(p.lambda, affine_bits(cp, 2 + m) + kRuiBits);
+  }
+}
+
+hipError_t reprice_launch(const RepriceParams& p, hipStream_t stream) {
+  const int n = (p.candEnd - p.candBegin) * p.nrefs;
+  if (n > 0)
+    hipLaunchKernelGGL(reprice_kernel, dim3((n + kSeededThreads - 1) / kSeededThreads), dim3(kSeededThreads), 0, stream,
+                       p);
   return hipGetLastError();
 }
 

@@ -27,10 +27,11 @@ namespace {
 
 // vame_affine_mc (ncus_dev NULL), vame_affine_mc_dev (ncus = the capacity)
 // and, over bi descriptors (CU = vame_mc_bicu), vame_affine_mc_bi
+// and vame_affine_mc_bi_p (preds non-NULL: the MVP instances of its kernels)
 template <typename CU>
 int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, const CU* cus,
               int ncus, const int32_t* ncus_dev, float lambda, uint16_t* pred, int64_t* cost, int32_t* bad,
-              void* stream) {
+              void* stream, const vame_cpmvs* preds = nullptr) {
   constexpr bool bi = std::is_same<CU, vame_mc_bicu>::value;
   if (!c || !refs || nrefs < 1 || nrefs > 4 || ncus < 0 || ncus > VAME_MC_MAX_CUS || !bad) return VAME_E_INVALID;
   if ((!pred && !cost) || (cost && !cur)) return VAME_E_INVALID;
@@ -58,7 +59,14 @@ int affine_mc(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int
   p.lambda = lambda;
   p.ncusDev = ncus_dev;
   if constexpr (bi) {
-    VAME_HIP(mc_bi_launch(p, (hipStream_t)stream));
+    if (preds) {
+      McBiParamsP pp;
+      static_cast<McBiParams&>(pp) = p;
+      pp.preds = reinterpret_cast<const int32_t*>(preds);
+      VAME_HIP(mc_bi_p_launch(pp, (hipStream_t)stream));
+    } else {
+      VAME_HIP(mc_bi_launch(p, (hipStream_t)stream));
+    }
   } else {
     VAME_HIP(mc_launch(p, c->prof, (hipStream_t)stream));
   }
@@ -137,10 +145,12 @@ int seed_search(vame_ctx* c, SeedParams& p, const uint16_t* cur, const uint16_t*
 // vame_affine_search and vame_bipred_refine: the same checks in the same
 // order and the same parameter block, but for the CU descriptor, the name of
 // the iteration count (P::*iters, at most maxIters) and the launch function.
-template <typename P, typename CU>
+// `launch` is any callable (const P&, hipStream_t) -> hipError_t: the stage's
+// launch function, or with_preds (below) for the _p forms.
+template <typename P, typename CU, typename Launch>
 int refine_cus(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, const CU* cus, int max_cus,
                const int32_t* ncus_dev, float lambda, int P::*iters, int niters, int maxIters, CU* out, int64_t* cost,
-               int32_t* bad, hipError_t (*launch)(const P&, hipStream_t), void* stream) {
+               int32_t* bad, Launch launch, void* stream) {
   if (!c || !cur || !refs || !cus || !out || !cost || !bad) return VAME_E_INVALID;
   if (nrefs < 1 || nrefs > 4 || niters < 0 || niters > maxIters || max_cus < 0 || max_cus > VAME_MC_MAX_CUS)
     return VAME_E_INVALID;
@@ -169,6 +179,21 @@ int refine_cus(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, in
   return VAME_OK;
 }
 
+// The launch of a _p call on a CU list: the block with the predictors and the
+// launch of their instances, or -- preds NULL, the zero predictor -- the
+// counterpart's own launch.
+template <typename PP, typename P>
+auto with_preds(const vame_cpmvs* preds, hipError_t (*launch)(const P&, hipStream_t),
+                hipError_t (*launch_p)(const PP&, hipStream_t)) {
+  return [=](const P& p, hipStream_t stream) {
+    if (!preds) return launch(p, stream);
+    PP pp;
+    static_cast<P&>(pp) = p;
+    pp.preds = reinterpret_cast<const int32_t*>(preds);
+    return launch_p(pp, stream);
+  };
+}
+
 // The in-frame candidates of the alignments a valid mode mask codes: their
 // range in the context's table.
 bool seeded_range(vame_ctx* c, int mode_mask, int& begin, int& end) {
@@ -177,6 +202,107 @@ bool seeded_range(vame_ctx* c, int mode_mask, int& begin, int& end) {
   begin = (preds & 3) ? 0 : c->biNCand[0];
   end = (preds & 12) ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
   return true;
+}
+
+// The predictor arrays of refIdx 0 .. nrefs-1 for the alignments with a PRED
+// in `preds` into a parameter block: each non-null.
+bool set_mvp(const int32_t* (&dst)[4][2], const vame_mvp* mvp, int nrefs, int preds) {
+  for (int r = 0; r < nrefs; r++)
+    for (int a = 0; a < 2; a++) {
+      if (!((preds >> (2 * a)) & 3)) continue;
+      if (!mvp->mv[r][a]) return false;
+      dst[r][a] = reinterpret_cast<const int32_t*>(mvp->mv[r][a]);
+    }
+  return true;
+}
+
+// vame_affine_me_seeded (mvp NULL) and vame_affine_me_seeded_p (which rejects a NULL mvp itself)
+int affine_me_seeded(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                     int mode_mask, int extra_grad_iter, vame_mv* const seed_mv[4][2],
+                     const vame_mvp* mvp, const vame_poc_result* res, void* work, size_t work_bytes, int32_t* bad,
+                     void* stream) {
+  if (!c || !cur || !refs || !seed_mv || !res || !work || !bad || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if (extra_grad_iter < 0 || extra_grad_iter > 64) return VAME_E_INVALID;
+  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(work)) & 7) return VAME_E_INVALID;
+  SeededParamsP p;
+  memset(&p, 0, sizeof(p));
+  if (!seeded_range(c, mode_mask, p.candBegin, p.candEnd)) return VAME_E_INVALID;
+  const int preds = vame_pred_mask(mode_mask);
+  if (!set_refs(p.search.refs, refs, nrefs)) return VAME_E_INVALID;
+  if (!set_result(p.cost, p.cpmv, res, nrefs, preds)) return VAME_E_INVALID;
+  for (int r = 0; r < nrefs; r++)
+    for (int a = 0; a < 2; a++) {
+      if (!((preds >> (2 * a)) & 3)) continue;
+      if (!seed_mv[r][a]) return VAME_E_INVALID;
+      p.seed[r][a] = reinterpret_cast<const int32_t*>(seed_mv[r][a]);
+    }
+  if (mvp && !set_mvp(p.mvp, mvp, nrefs, preds)) return VAME_E_INVALID;
+  p.with3 = (mode_mask & VAME_MODE_3CP) != 0;
+  p.cap = nrefs * (p.candEnd - p.candBegin);
+  if (work_bytes < (mvp ? seeded_p_work_bytes((size_t)p.cap, p.with3) : seeded_work_bytes((size_t)p.cap, p.with3)))
+    return VAME_E_INVALID;
+  if (c->prof) return VAME_E_UNSUPPORTED;  // no PROF form
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cands = c->biCands;
+  p.work = seeded_work(work, (size_t)p.cap, p.with3);
+  p.preds = reinterpret_cast<int32_t*>(static_cast<char*>(work) + seeded_work_bytes((size_t)p.cap, p.with3));
+  p.search.cur = cur;
+  p.search.bad = bad;
+  p.search.nrefs = nrefs;
+  p.search.W = c->W;
+  p.search.H = c->H;
+  p.search.extra = extra_grad_iter;
+  p.search.lambda = lambda;
+  if (mvp)
+    VAME_HIP(seeded_p_launch(p, (hipStream_t)stream));
+  else
+    VAME_HIP(seeded_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+// vame_bipred (mvp NULL) and vame_bipred_p (which rejects a NULL mvp itself)
+int bipred(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+           const vame_poc_result* res, int pred_mask, const vame_mvp* mvp, int64_t* const bi_cost[2],
+           int32_t* const bi_sel[2], void* stream) {
+  if (!c || !cur || !refs || !res || nrefs < 1 || nrefs > 4 || !bi_cost || !bi_sel) return VAME_E_INVALID;
+  if ((pred_mask & ~15) || !pred_mask) return VAME_E_INVALID;
+  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
+  BiRowsParamsP p;
+  memset(&p, 0, sizeof(p));
+  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
+  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
+  const bool on[2] = {(pred_mask & 3) != 0, (pred_mask & 12) != 0};
+  for (int a = 0; a < 2; a++) {
+    if (!on[a]) continue;
+    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
+    p.biCost[a] = bi_cost[a];
+    p.biSel[a] = bi_sel[a];
+  }
+  if (mvp && !set_mvp(p.mvp, mvp, nrefs, pred_mask)) return VAME_E_INVALID;
+  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  p.cur = cur;
+  p.cands = c->biCands;
+  p.groupCand = c->biGroupCand;
+  p.pairSatd = c->biPairSatd;
+  p.candBegin = on[0] ? 0 : c->biNCand[0];
+  p.candEnd = on[1] ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
+  p.groupBegin = on[0] ? 0 : c->biNGroup[0];
+  p.groupEnd = on[1] ? c->biNGroup[0] + c->biNGroup[1] : c->biNGroup[0];
+  p.rowsOf[0] = c->nCtus * kFullCusPerCtu;
+  p.rowsOf[1] = c->nCtus * kHalfCusPerCtu;
+  p.nrefs = nrefs;
+  p.predMask = pred_mask;
+  p.W = c->W;
+  p.H = c->H;
+  p.lambda = lambda;
+  if (mvp)
+    VAME_HIP(bipred_p_launch(p, (hipStream_t)stream));
+  else
+    VAME_HIP(bipred_launch(p, (hipStream_t)stream));
+  return VAME_OK;
 }
 
 }  // namespace
@@ -212,40 +338,7 @@ int vame_affine_mc_bi(vame_ctx* c, const uint16_t* cur, const uint16_t* const* r
 int vame_bipred(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
                 const vame_poc_result* res, int pred_mask, int64_t* const bi_cost[2], int32_t* const bi_sel[2],
                 void* stream) {
-  if (!c || !cur || !refs || !res || nrefs < 1 || nrefs > 4 || !bi_cost || !bi_sel) return VAME_E_INVALID;
-  if ((pred_mask & ~15) || !pred_mask) return VAME_E_INVALID;
-  if (reinterpret_cast<uintptr_t>(cur) & 7) return VAME_E_INVALID;
-  BiRowsParams p;
-  memset(&p, 0, sizeof(p));
-  if (!set_refs(p.refs, refs, nrefs)) return VAME_E_INVALID;
-  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
-  const bool on[2] = {(pred_mask & 3) != 0, (pred_mask & 12) != 0};
-  for (int a = 0; a < 2; a++) {
-    if (!on[a]) continue;
-    if (!bi_cost[a] || !bi_sel[a]) return VAME_E_INVALID;
-    p.biCost[a] = bi_cost[a];
-    p.biSel[a] = bi_sel[a];
-  }
-  if (c->prof) return VAME_E_UNSUPPORTED;  // PROF has no bi form
-  DeviceGuard guard(c->device);
-  VAME_HIP(guard.err);
-  p.cur = cur;
-  p.cands = c->biCands;
-  p.groupCand = c->biGroupCand;
-  p.pairSatd = c->biPairSatd;
-  p.candBegin = on[0] ? 0 : c->biNCand[0];
-  p.candEnd = on[1] ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
-  p.groupBegin = on[0] ? 0 : c->biNGroup[0];
-  p.groupEnd = on[1] ? c->biNGroup[0] + c->biNGroup[1] : c->biNGroup[0];
-  p.rowsOf[0] = c->nCtus * kFullCusPerCtu;
-  p.rowsOf[1] = c->nCtus * kHalfCusPerCtu;
-  p.nrefs = nrefs;
-  p.predMask = pred_mask;
-  p.W = c->W;
-  p.H = c->H;
-  p.lambda = lambda;
-  VAME_HIP(bipred_launch(p, (hipStream_t)stream));
-  return VAME_OK;
+  return bipred(c, cur, refs, nrefs, lambda, res, pred_mask, nullptr, bi_cost, bi_sel, stream);
 }
 
 int vame_partition_bi(vame_ctx* c, const vame_poc_result* res, int nrefs, int pred_mask, int64_t split_penalty,
@@ -329,37 +422,90 @@ size_t vame_seeded_work_bytes(vame_ctx* c, int nrefs, int mode_mask) {
 int vame_affine_me_seeded(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
                           int mode_mask, int extra_grad_iter, vame_mv* const seed_mv[4][2],
                           const vame_poc_result* res, void* work, size_t work_bytes, int32_t* bad, void* stream) {
-  if (!c || !cur || !refs || !seed_mv || !res || !work || !bad || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
-  if (extra_grad_iter < 0 || extra_grad_iter > 64) return VAME_E_INVALID;
-  if ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(work)) & 7) return VAME_E_INVALID;
-  SeededParams p;
+  return affine_me_seeded(c, cur, refs, nrefs, lambda, mode_mask, extra_grad_iter, seed_mv, nullptr, res, work,
+                          work_bytes, bad, stream);
+}
+
+// ---- rates against a predictor
+int vame_affine_mc_bi_p(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                        const vame_mc_bicu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                        float lambda, uint16_t* pred, int64_t* cost, int32_t* bad, void* stream) {
+  return affine_mc(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, pred, cost, bad, stream, preds);
+}
+
+int vame_affine_search_p(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                         const vame_mc_cu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                         float lambda, int extra_grad_iter, vame_mc_cu* out, int64_t* cost, int32_t* bad,
+                         void* stream) {
+  return refine_cus(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, &SearchParams::extra, extra_grad_iter, 64, out,
+                    cost, bad, with_preds(preds, search_launch, search_p_launch), stream);
+}
+
+int vame_bipred_refine_p(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs,
+                         const vame_mc_bicu* cus, const vame_cpmvs* preds, int max_cus, const int32_t* ncus_dev,
+                         float lambda, int rounds, vame_mc_bicu* out, int64_t* cost, int32_t* bad, void* stream) {
+  return refine_cus(c, cur, refs, nrefs, cus, max_cus, ncus_dev, lambda, &BiRefineParams::rounds, rounds, 4, out, cost,
+                    bad, with_preds(preds, birefine_launch, birefine_p_launch), stream);
+}
+
+int vame_reprice(vame_ctx* c, int nrefs, float lambda, int pred_mask, const vame_mvp* mvp, const vame_poc_result* res,
+                 int32_t* bad, void* stream) {
+  if (!c || !mvp || !res || !bad || nrefs < 1 || nrefs > 4) return VAME_E_INVALID;
+  if ((pred_mask & ~15) || !pred_mask) return VAME_E_INVALID;
+  RepriceParams p;
   memset(&p, 0, sizeof(p));
-  if (!seeded_range(c, mode_mask, p.candBegin, p.candEnd)) return VAME_E_INVALID;
-  const int preds = vame_pred_mask(mode_mask);
-  if (!set_refs(p.search.refs, refs, nrefs)) return VAME_E_INVALID;
-  if (!set_result(p.cost, p.cpmv, res, nrefs, preds)) return VAME_E_INVALID;
-  for (int r = 0; r < nrefs; r++)
-    for (int a = 0; a < 2; a++) {
-      if (!((preds >> (2 * a)) & 3)) continue;
-      if (!seed_mv[r][a]) return VAME_E_INVALID;
-      p.seed[r][a] = reinterpret_cast<const int32_t*>(seed_mv[r][a]);
-    }
-  p.with3 = (mode_mask & VAME_MODE_3CP) != 0;
-  p.cap = nrefs * (p.candEnd - p.candBegin);
-  if (work_bytes < seeded_work_bytes((size_t)p.cap, p.with3)) return VAME_E_INVALID;
-  if (c->prof) return VAME_E_UNSUPPORTED;  // no PROF form
+  if (!set_result(p.cost, p.cpmv, res, nrefs, pred_mask)) return VAME_E_INVALID;
+  if (!set_mvp(p.mvp, mvp, nrefs, pred_mask)) return VAME_E_INVALID;
   DeviceGuard guard(c->device);
   VAME_HIP(guard.err);
   p.cands = c->biCands;
-  p.work = seeded_work(work, (size_t)p.cap, p.with3);
-  p.search.cur = cur;
-  p.search.bad = bad;
-  p.search.nrefs = nrefs;
-  p.search.W = c->W;
-  p.search.H = c->H;
-  p.search.extra = extra_grad_iter;
-  p.search.lambda = lambda;
-  VAME_HIP(seeded_launch(p, (hipStream_t)stream));
+  p.candBegin = (pred_mask & 3) ? 0 : c->biNCand[0];
+  p.candEnd = (pred_mask & 12) ? c->biNCand[0] + c->biNCand[1] : c->biNCand[0];
+  p.bad = bad;
+  p.nrefs = nrefs;
+  p.lambda = lambda;
+  VAME_HIP(reprice_launch(p, (hipStream_t)stream));
+  return VAME_OK;
+}
+
+size_t vame_seeded_p_work_bytes(vame_ctx* c, int nrefs, int mode_mask) {
+  int begin, end;
+  if (!c || nrefs < 1 || nrefs > 4 || !seeded_range(c, mode_mask, begin, end)) return 0;
+  return seeded_p_work_bytes((size_t)nrefs * (end - begin), (mode_mask & VAME_MODE_3CP) != 0);
+}
+
+int vame_affine_me_seeded_p(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                            int mode_mask, int extra_grad_iter, vame_mv* const seed_mv[4][2], const vame_mvp* mvp,
+                            const vame_poc_result* res, void* work, size_t work_bytes, int32_t* bad, void* stream) {
+  if (!mvp) return VAME_E_INVALID;
+  return affine_me_seeded(c, cur, refs, nrefs, lambda, mode_mask, extra_grad_iter, seed_mv, mvp, res, work,
+                          work_bytes, bad, stream);
+}
+
+int vame_bipred_p(vame_ctx* c, const uint16_t* cur, const uint16_t* const* refs, int nrefs, float lambda,
+                  const vame_poc_result* res, int pred_mask, const vame_mvp* mvp, int64_t* const bi_cost[2],
+                  int32_t* const bi_sel[2], void* stream) {
+  if (!mvp) return VAME_E_INVALID;
+  return bipred(c, cur, refs, nrefs, lambda, res, pred_mask, mvp, bi_cost, bi_sel, stream);
+}
+
+int vame_mvp_gather(vame_ctx* c, const vame_mvp* mvp, const vame_mc_bicu* cus, int max_cus, const int32_t* ncus_dev,
+                    vame_cpmvs* preds, void* stream) {
+  if (!c || !mvp || !cus || !preds || max_cus < 0 || max_cus > VAME_MC_MAX_CUS) return VAME_E_INVALID;
+  if (max_cus == 0) return VAME_OK;
+  DeviceGuard guard(c->device);
+  VAME_HIP(guard.err);
+  MvpGatherParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < 4; r++)
+    for (int a = 0; a < 2; a++) p.mvp[r][a] = reinterpret_cast<const int32_t*>(mvp->mv[r][a]);
+  p.cus = reinterpret_cast<const McBiCu*>(cus);
+  p.preds = reinterpret_cast<int32_t*>(preds);
+  p.ncusDev = ncus_dev;
+  p.maxCus = max_cus;
+  p.ctusPerRow = c->ctusPerRow;
+  p.nCtus = c->nCtus;
+  VAME_HIP(mvp_gather_launch(p, (hipStream_t)stream));
   return VAME_OK;
 }
 

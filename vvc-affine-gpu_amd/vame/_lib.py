@@ -23,7 +23,8 @@ EXPORTS = (
     "vame_affine_mc_dev", "vame_partition", "vame_partition_table", "vame_affine_mc_bi", "vame_bipred",
     "vame_partition_bi", "vame_bipred_refine", "vame_seed_search", "vame_affine_search",
     "vame_seeded_work_bytes", "vame_affine_me_seeded", "vame_seed_pyramid_bytes", "vame_seed_pyramid",
-    "vame_seed_search_wide",
+    "vame_seed_search_wide", "vame_affine_mc_bi_p", "vame_affine_search_p", "vame_bipred_refine_p", "vame_reprice",
+    "vame_seeded_p_work_bytes", "vame_affine_me_seeded_p", "vame_bipred_p", "vame_mvp_gather",
 )
 
 
@@ -38,6 +39,11 @@ class PocResult(ctypes.Structure):
 class SeedResult(ctypes.Structure):
     """vame_seed_result (include/vame.h): [refIdx][align]."""
     _fields_ = [("mv", (ctypes.c_void_p * 2) * 4), ("cost", (ctypes.c_void_p * 2) * 4)]
+
+
+class Mvp(ctypes.Structure):
+    """vame_mvp (include/vame.h): [refIdx][align]."""
+    _fields_ = [("mv", (ctypes.c_void_p * 2) * 4)]
 
 
 class PocJob(ctypes.Structure):
@@ -82,6 +88,16 @@ def lib():
         L.vame_seeded_work_bytes.restype = ctypes.c_size_t
         L.vame_affine_me_seeded.argtypes = [P, P, P, I, F, I, I, P, ctypes.POINTER(PocResult), P, ctypes.c_size_t,
                                             P, P]
+        L.vame_affine_mc_bi_p.argtypes = [P, P, P, I, P, P, I, P, F, P, P, P, P]
+        L.vame_affine_search_p.argtypes = [P, P, P, I, P, P, I, P, F, I, P, P, P, P]
+        L.vame_bipred_refine_p.argtypes = [P, P, P, I, P, P, I, P, F, I, P, P, P, P]
+        L.vame_reprice.argtypes = [P, I, F, I, ctypes.POINTER(Mvp), ctypes.POINTER(PocResult), P, P]
+        L.vame_seeded_p_work_bytes.argtypes = [P, I, I]
+        L.vame_seeded_p_work_bytes.restype = ctypes.c_size_t
+        L.vame_affine_me_seeded_p.argtypes = [P, P, P, I, F, I, I, P, ctypes.POINTER(Mvp), ctypes.POINTER(PocResult), P,
+                                              ctypes.c_size_t, P, P]
+        L.vame_bipred_p.argtypes = [P, P, P, I, F, ctypes.POINTER(PocResult), I, ctypes.POINTER(Mvp), P, P, P]
+        L.vame_mvp_gather.argtypes = [P, ctypes.POINTER(Mvp), P, I, P, P, P]
         L.vame_num_ctus.argtypes = [I, I]
         L.vame_cus_per_ctu.argtypes = [I]
         L.vame_num_groups.argtypes = [I]

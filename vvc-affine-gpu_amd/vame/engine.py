@@ -16,7 +16,7 @@ import ctypes
 
 import torch
 
-from ._lib import PocJob, PocResult, SeedResult, check, lib
+from ._lib import Mvp, PocJob, PocResult, SeedResult, check, lib
 
 CPMV_FIELDS = ("nCPs", "LTx", "LTy", "RTx", "RTy", "LBx", "LBy")
 MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
@@ -690,6 +690,213 @@ class Engine:
                                           ptrs, ctypes.byref(pr), _ptr(work), work.numel() * 8, _ptr(bad),
                                           self._stream()))
         return result, bad
+
+    # ---- rates against a motion-vector predictor
+    def _check_preds(self, preds: torch.Tensor | None, n: int, what: str):
+        """The predictors of a descriptor-list call: None (the zero predictor)
+        or a contiguous int32 [n, 7] tensor (vame_cpmvs; nCPs ignored)."""
+        if preds is not None and (preds.dtype != torch.int32 or tuple(preds.shape) != (n, 7)
+                                  or preds.device != self.device or not preds.is_contiguous()):
+            raise ValueError(f"{what}: preds must be a contiguous int32 [{n}, 7] tensor on {self.device}")
+
+    def _mvp(self, mvp: dict, nrefs: int, preds: int, what: str) -> Mvp:
+        """{(r, a): int32 [n, 2]} (seed_search()["mv"], region_predictors()) as a
+        vame_mvp: every (r, alignment) with a PRED in `preds` must be there."""
+        out = Mvp()
+        for r in range(nrefs):
+            for a in (0, 1):
+                if (preds >> (2 * a)) & 3:
+                    t = mvp.get((r, a)) if isinstance(mvp, dict) else None
+                    out.mv[r][a] = self._check_seed(t, a, f"{what}: mvp[{(r, a)}]", torch.int32, (2,)).data_ptr()
+        return out
+
+    def affine_mc_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, lam: float = 0.0,
+                    cur: torch.Tensor | None = None, pred: torch.Tensor | None = None, want_cost: bool = False,
+                    ncus: torch.Tensor | None = None):
+        """vame_affine_mc_bi_p: affine_mc_bi whose cost prices every hypothesis
+        against a predictor, floor(lam * (bits_p + 2)) per hypothesis (include/
+        vame.h).  cus: int32 [n, 20] (vame.bipred.BICU_FIELDS) with preds int32
+        [2n, 7], hypothesis h of descriptor i at row 2i + h (the second is not
+        read for a uni descriptor), or int32 [n, 12] (vame.mc.CU_FIELDS) with
+        preds [n, 7]: those are widened to uni bi descriptors on the device.
+        A predictor row is (nCPs -- ignored --, LTx, LTy, RTx, RTy, LBx, LBy),
+        components in [-2^17, 2^17 - 1]; one out of range makes its descriptor
+        invalid.  preds None: the zero predictor, affine_mc_bi's outputs bit
+        for bit.  The samples do not depend on the predictor.  Returns (pred,
+        cost, bad) as affine_mc.  Not available under PROF."""
+        if cus.dim() == 2 and cus.shape[1] == 12:
+            self._check_cus(cus, 12)
+            self._check_preds(preds, cus.shape[0], "affine_mc_p")
+            wide = torch.zeros((cus.shape[0], 20), dtype=torch.int32, device=self.device)
+            wide[:, :12] = cus
+            wide[:, 12] = -1
+            if preds is not None:
+                p2 = torch.zeros((cus.shape[0], 2, 7), dtype=torch.int32, device=self.device)
+                p2[:, 0] = preds
+                preds = p2.reshape(-1, 7)
+            cus = wide
+        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc_p", 20, cus, refs, cur, pred, want_cost, ncus)
+        n = cus.shape[0]
+        self._check_preds(preds, 2 * n, "affine_mc_p")
+        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_affine_mc_bi_p(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), _ptr(preds), n, _ptr(ncus),
+                                        float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+        return pred, cost, bad
+
+    def affine_search_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, cur, lam: float, extra: int = 0,
+                        ncus: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                        cost: torch.Tensor | None = None):
+        """vame_affine_search_p: affine_search with the rate of every iteration
+        taken against preds[i] (int32 [n, 7], as affine_mc_p), so the predictor
+        takes part in which iteration wins.  cost is affine_mc_p's cost of out
+        with the same predictors.  preds None: affine_search bit for bit."""
+        self._check_cus(cus, 12)
+        if not 0 <= int(extra) <= 64:
+            raise ValueError("extra must be in 0..64")
+        refs, ref_ptrs = self._refs(refs, "affine_search_p")
+        cur = self._frame(cur)
+        n = cus.shape[0]
+        self._check_preds(preds, n, "affine_search_p")
+        self._check_scalar(ncus, "ncus")
+        out, cost = self._refine_out(cus, out, cost)
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_affine_search_p(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), _ptr(preds), n, _ptr(ncus),
+                                         float(lam), int(extra), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
+        return out, cost, bad
+
+    def bipred_refine_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, cur, lam: float, rounds: int = 2,
+                        count: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                        cost: torch.Tensor | None = None):
+        """vame_bipred_refine_p: bipred_refine with hypothesis h of descriptor i
+        priced against preds[2i + h] (int32 [2n, 7]) in the start cost and in
+        every comparison.  The cost never rises and is affine_mc_p's cost of
+        out.  preds None: bipred_refine bit for bit."""
+        self._check_cus(cus, 20)
+        if not 0 <= int(rounds) <= 4:
+            raise ValueError("rounds must be in 0..4")
+        refs, ref_ptrs = self._refs(refs, "bipred_refine_p")
+        cur = self._frame(cur)
+        n = cus.shape[0]
+        self._check_preds(preds, 2 * n, "bipred_refine_p")
+        self._check_scalar(count, "count")
+        out, cost = self._refine_out(cus, out, cost)
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_bipred_refine_p(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), _ptr(preds), n,
+                                         _ptr(count), float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad),
+                                         self._stream()))
+        return out, cost, bad
+
+    def reprice(self, lam: float, result: dict, mvp: dict, preds: int | None = None):
+        """vame_reprice: replace, in place, the zero-predictor rate in the costs
+        of `result` (an alloc_poc dict as the search filled it, same lam) by
+        the rate against each row's predictor mvp[(r, a)][row] (LT = RT = LB):
+        every in-frame row of every PRED in `preds` (None: all the dict
+        holds).  CPMVs are untouched.  A second call prices twice.  Returns
+        (result, bad): bad is 1 when a predictor was out of range (its row is
+        skipped).  Pure arithmetic; reads nothing on the host."""
+        from . import partition as P
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds:
+            raise ValueError("preds must hold a PRED and only bits 0..3")
+        nrefs, pr = self._check_result(result, preds, "reprice")
+        m = self._mvp(mvp, nrefs, preds, "reprice")
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_reprice(self._h, nrefs, float(lam), preds, ctypes.byref(m), ctypes.byref(pr), _ptr(bad),
+                                 self._stream()))
+        return result, bad
+
+    def affine_me_seeded_p(self, cur, refs, lam: float, result: dict, seeds: dict, mvp: dict, modes: int = 3,
+                           extra: int = 0):
+        """vame_affine_me_seeded_p: affine_me_seeded whose two searches price
+        against the row's predictor mvp[(r, a)][row]; `result` is expected
+        re-priced under the same mvp (reprice()).  With an all-zero mvp it is
+        affine_me_seeded bit for bit.  Returns (result, bad): bad is 1 when a
+        seed or a predictor was out of range (its row is skipped)."""
+        cur = self._frame(cur)
+        refs, ref_ptrs = self._refs(refs, "affine_me_seeded_p")
+        if not int(modes) & MODE_2CP or int(modes) & ~15:
+            raise ValueError("modes must hold MODE_2CP and only bits 0..3")
+        if not 0 <= int(extra) <= 64:
+            raise ValueError("extra must be in 0..64")
+        preds = pred_mask(modes)
+        nrefs, pr = self._check_result(result, preds, "affine_me_seeded_p")
+        if nrefs != len(refs):
+            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
+        ptrs = ((ctypes.c_void_p * 2) * 4)()
+        for r in range(nrefs):
+            for a in (0, 1):
+                if (preds >> (2 * a)) & 3:
+                    t = seeds.get((r, a)) if isinstance(seeds, dict) else None
+                    ptrs[r][a] = self._check_seed(t, a, f"seeds[{(r, a)}]", torch.int32, (2,)).data_ptr()
+        m = self._mvp(mvp, nrefs, preds, "affine_me_seeded_p")
+        nbytes = lib().vame_seeded_p_work_bytes(self._h, nrefs, int(modes))
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        check(lib().vame_affine_me_seeded_p(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), int(modes), int(extra),
+                                            ptrs, ctypes.byref(m), ctypes.byref(pr), _ptr(work), work.numel() * 8,
+                                            _ptr(bad), self._stream()))
+        return result, bad
+
+    def bipred_p(self, cur, refs, lam: float, result: dict, mvp: dict, preds: int | None = None,
+                 out: dict | None = None):
+        """vame_bipred_p: bipred whose bi cost prices hypothesis r against the
+        row's predictor mvp[(r, a)][row]; the hypotheses are still picked by
+        the costs of `result`, which the caller has re-priced (reprice()).  A
+        row with a predictor out of range keeps INT64_MAX and -1.  Arguments
+        and the returned dict as bipred."""
+        from . import bipred as B
+        from . import partition as P
+        cur = self._frame(cur)
+        refs, ref_ptrs = self._refs(refs, "bipred_p")
+        if not result:
+            raise ValueError("bipred_p needs a result dict")
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds:
+            raise ValueError("preds must hold a PRED and only bits 0..3")
+        nrefs, pr = self._check_result(result, preds, "bipred_p")
+        if nrefs != len(refs):
+            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
+        m = self._mvp(mvp, nrefs, preds, "bipred_p")
+        if out is None:
+            full = B.alloc_bi(self.n_ctus, self.device)
+            out = {k: [t if (preds >> (2 * a)) & 3 else None for a, t in enumerate(full[k])] for k in ("cost", "sel")}
+        cost, sel = self._check_bi(out, preds)
+        check(lib().vame_bipred_p(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds,
+                                  ctypes.byref(m), cost, sel, self._stream()))
+        return out
+
+    def leaf_predictors(self, part: dict, mvp: dict, out: torch.Tensor | None = None) -> torch.Tensor:
+        """vame_mvp_gather on the leaves of a partition() or partition_bi()
+        result, their count read on the device: int32 [2 * nCtus*64, 7], the
+        predictor of hypothesis h of leaf i at row 2i + h -- the mvp row of
+        (ref, alignment, candidate row) expanded to LT = RT = LB, zero where
+        the leaf is no candidate CU or mvp holds no array for (ref,
+        alignment).  Uni leaves of partition() (12 columns) are widened on the
+        device; affine_mc_p takes cus[:, :12] with rows 0::2, or the widened
+        form.  Rows of leaves past the count are not written (zero in a new
+        tensor).  No host read; asynchronous on the current stream."""
+        cus = part["cus"]
+        if cus.dim() == 2 and cus.shape[1] == 12:
+            self._check_cus(cus, 12)
+            wide = torch.zeros((cus.shape[0], 20), dtype=torch.int32, device=self.device)
+            wide[:, :12] = cus
+            wide[:, 12] = -1
+            cus = wide
+        self._check_cus(cus, 20)
+        n = cus.shape[0]
+        self._check_scalar(part["ncus"], "ncus")
+        if out is None:
+            out = torch.zeros((2 * n, 7), dtype=torch.int32, device=self.device)
+        self._check_preds(out, 2 * n, "leaf_predictors")
+        m = Mvp()
+        for (r, a), t in mvp.items():
+            if not (0 <= r < 4 and a in (0, 1)):
+                raise ValueError(f"unexpected mvp key {(r, a)}")
+            m.mv[r][a] = self._check_seed(t, a, f"mvp[{(r, a)}]", torch.int32, (2,)).data_ptr()
+        check(lib().vame_mvp_gather(self._h, ctypes.byref(m), _ptr(cus), n, _ptr(part["ncus"]), _ptr(out),
+                                    self._stream()))
+        return out
 
     def affine_me_poc(self, cur, refs, lam: float, modes: int = 3, extra: int = 0, out=None):
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to

@@ -49,7 +49,7 @@ def main():
     frames = cfg["frames"] if n_pairs is None else frames_for_pairs(n_pairs)
     run = ShardRun(eng, cfg["W"], cfg["H"], qp, frames, cfg["modes"], args.gpus, args.rank_only, dev,
                    n_pairs=n_pairs)
-    cnt = (ctypes.c_ulonglong * 20)()
+    cnt = (ctypes.c_ulonglong * 24)()
     L.vame_debug_pred_count(cnt, 1)
     run.step()
     torch.cuda.synchronize()
@@ -72,7 +72,17 @@ def main():
            # several CUs (lanes of settled CUs idle while the wave iterates)
            "lane_use_quad": cnt[0] / max(cnt[12], 1), "lane_use_ctu": cnt[1] / max(cnt[13], 1),
            "multi_cu_wave_slots_frac_quad": cnt[14] / max(cnt[12], 1),
-           "multi_cu_wave_lane_use_quad": cnt[16] / max(cnt[14], 1)}
+           "multi_cu_wave_lane_use_quad": cnt[16] / max(cnt[14], 1),
+           # the quadrant kernel's autonomous two-sub-block waves of CUs of 32 / 64
+           # sub-blocks: wave-iterations run, those after iteration 0 (and at it)
+           # whose live CUs held <= 64 sub-blocks, the lane use of their prediction
+           # passes, and the wave-iterations run one sub-block per lane after a
+           # hand-over; the other multi-CU waves' lane use (one-sub-block body)
+           "sbl2_wave_iters_quad": cnt[18], "sbl2_wave_iters_le64_quad": cnt[19],
+           "sbl2_wave_iters_le64_iter0_quad": cnt[20],
+           "sbl2_wave_lane_use_quad": cnt[22] / max(cnt[21], 1),
+           "sbl2_wave_iters_relaid_quad": cnt[23],
+           "sbl1_multi_cu_wave_lane_use_quad": (cnt[16] - cnt[22]) / max(cnt[14] - cnt[21], 1)}
     print(json.dumps(out))
     eng.close()
 

@@ -37,24 +37,45 @@ namespace vame {
 // (the clamped-global path); [12 + kernel]: 64 lane slots per wave that runs a
 // prediction step, [14 + kernel] / [16 + kernel]: the same slots and the
 // predictions run, of waves holding several CUs (autonomous, < 64 sub-blocks
-// per CU) -- the lanes an iteration spends on settled CUs.
+// per CU) -- the lanes an iteration spends on settled CUs.  [18 ..]: the
+// quadrant kernel's autonomous two-sub-block wave tasks of CUs of 32 or 64
+// sub-blocks: [18] the wave-iterations that ran a prediction step, [19] those
+// of them after iteration 0 whose live CUs held <= 64 sub-blocks (what the
+// hand-over to one sub-block per lane can take), [20] the same at iteration 0
+// (tasks with CUs outside the frame or fewer CUs than a wave holds), [21] the
+// lane slots of their prediction passes (64 per pass), [22] the predictions
+// run in them, [23] the wave-iterations run after a hand-over.
 #ifndef VAME_COUNT_PRED
 #define VAME_COUNT_PRED 0
 #endif
 #if VAME_COUNT_PRED
-__device__ unsigned long long g_pred_count[20];
-#define PC_DECL unsigned pc_n = 0, pc_w = 0, pc_mw = 0, pc_me = 0;
+__device__ unsigned long long g_pred_count[24];
+#define PC_DECL unsigned pc_n = 0, pc_w = 0, pc_mw = 0, pc_me = 0, pc2[6] = {};
 #define PC_ADD                                                           \
   {                                                                      \
     pc_n++;                                                              \
     const unsigned long long m_ = __builtin_amdgcn_ballot_w64(true);     \
     if (__lane_id() == __builtin_ctzll(m_)) {                            \
       pc_w += 64;                                                        \
-      if (!coop && logS < 6) {                                           \
+      if (!coop && pcLogS < 6) {                                         \
         pc_mw += 64;                                                     \
         pc_me += __popcll(m_);                                           \
       }                                                                  \
     }                                                                    \
+  }
+// one call per iteration of an autonomous two-sub-block quadrant wave of CUs of
+// 32 or 64 sub-blocks: m_ the lanes that predict, per_ the sub-blocks each runs
+#define PC2_ITER(m_, per_, iter_)                                                        \
+  {                                                                                      \
+    const unsigned long long l_ = (m_);                                                  \
+    if (l_ && __lane_id() == __builtin_ctzll(l_)) {                                      \
+      const unsigned sb_ = (unsigned)__popcll(l_) * (per_); /* live sub-blocks */        \
+      pc2[0]++;                                                                          \
+      if (sb_ <= 64u) pc2[(iter_) == 0 ? 2 : 1]++;                                       \
+      pc2[3] += 64u * (per_);                                                            \
+      pc2[4] += sb_;                                                                     \
+      if ((per_) == 1) pc2[5]++;                                                         \
+    }                                                                                    \
   }
 #define PC_FLUSH                                                                                \
   {                                                                                             \
@@ -62,10 +83,13 @@ __device__ unsigned long long g_pred_count[20];
     if (pc_w) atomicAdd(&g_pred_count[12 + (REGION == 128)], (unsigned long long)pc_w);        \
     if (pc_mw) atomicAdd(&g_pred_count[14 + (REGION == 128)], (unsigned long long)pc_mw);      \
     if (pc_me) atomicAdd(&g_pred_count[16 + (REGION == 128)], (unsigned long long)pc_me);      \
+    for (int i_ = 0; i_ < 6; i_++)                                                              \
+      if (pc2[i_]) atomicAdd(&g_pred_count[18 + i_], (unsigned long long)pc2[i_]);              \
   }
 #else
 #define PC_DECL
 #define PC_ADD
+#define PC2_ITER(m_, per_, iter_)
 #define PC_FLUSH
 #endif
 

@@ -88,6 +88,26 @@ struct Cfg {
   static constexpr bool STASH = KIND != kKindQuad2 && !HALF2;
 };
 
+// The hand-over of a two-sub-block wave task (affine_me_quad in 2-CP-only
+// launches, vame_kernel.h): once the task's live CUs together hold <= 64
+// sub-blocks, the wave's 64 lanes run them one sub-block per lane.  liveCus has
+// bit k set for a live CU in slot k of the task (k < kTaskCu), logNsb is log2
+// of a CU's sub-blocks (5 or 6; a task holds CUs of one size).  Live CU number
+// r (slots ascending) takes the aligned segment of 2^logNsb lanes from
+// r << logNsb, its sub-blocks in raster order.
+constexpr bool relayout_fits(unsigned liveCus, int logNsb) {
+  return liveCus != 0 && (__builtin_popcount(liveCus) << logNsb) <= 64;
+}
+struct RelayoutLane {
+  int cu;  // the lane's CU: its slot in the task, or -1 for a lane without one
+  int sb;  // its sub-block in the CU (raster order)
+};
+constexpr RelayoutLane relayout_lane(int lane, unsigned liveCus, int logNsb) {
+  // at most two segments fit a wave: the lane's rank among the live CUs is 0 or 1
+  const unsigned m = (lane >> logNsb) ? liveCus & (liveCus - 1) : liveCus;
+  return {m ? __builtin_ctz(m) : -1, lane & ((1 << logNsb) - 1)};
+}
+
 // A candidate CU of the frame's fixed geometry that lies wholly in the frame
 // (vame_templates.cpp builds the table: the aligned candidates first, CTUs
 // ascending, rows ascending, then the half-aligned ones).

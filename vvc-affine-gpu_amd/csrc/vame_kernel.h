@@ -58,6 +58,14 @@
 #include "vame_dev.h"
 #include "vame_items.h"
 
+// VAME_RELAYOUT (compile-time, default on): the 2-CP-only launches' two-sub-block
+// quadrant waves hand their last live CUs over to one sub-block per lane
+// (affine_me_body, kRelay).  `make variant NAME=norelayout DEFS=-DVAME_RELAYOUT=0`
+// builds the A/B partner without it.
+#ifndef VAME_RELAYOUT
+#define VAME_RELAYOUT 1
+#endif
+
 namespace vame {
 
 // One (POC, refIdx) pair of a launch: the reference's kernel arguments for it
@@ -610,6 +618,40 @@ __device__ __forceinline__ TaskCtx task_lanes(const ItemCtx& w, int tid, bool co
   return t;
 }
 
+// The hand-over of an autonomous two-sub-block task whose live CUs (liveCus:
+// bit k for slot cuB + k) together hold <= 64 sub-blocks: the wave's lanes
+// take them one sub-block per lane (relayout_lane, vame_items.h), each live CU
+// an aligned segment of its 32 or 64 sub-blocks in raster order; the CUs keep
+// their slots, so their state, moments and systems stay where they are.  The
+// lane's prediction rows (sbIdx) are the wave's own as before, the rows above
+// and below now sbCols lanes away in both s_top and s_bot.
+__device__ __forceinline__ void relayout_task(const ItemCtx& w, unsigned liveCus, const CuSlot* s_cu, TaskCtx& t) {
+  const int logNsb = t.logL + 1;
+  const RelayoutLane rl = relayout_lane((int)__lane_id(), liveCus, logNsb);
+  t.logL = t.logS = logNsb;
+  t.myCu = rl.cu < 0 ? -1 : t.cuB + rl.cu;
+  t.local = rl.sb;
+  t.sbIdx = t.myCu >= 0 ? t.tid : 0;  // (a lane without a CU so far had none)
+  t.g.x = t.g.y = t.g.lw = t.g.lh = t.g.w = t.g.h = 0;
+  t.sx = 0;
+  t.sy = 0;
+  t.sbCols = 1;
+  t.active = t.myCu >= 0;  // a live CU lies inside the frame
+  if (t.myCu >= 0) {
+    const CuSlot cs = s_cu[t.myCu];
+    t.g.lw = cs.lw;
+    t.g.lh = cs.lh;
+    t.g.w = 1 << t.g.lw;
+    t.g.h = 1 << t.g.lh;
+    t.g.x = w.ctuX + cs.x;
+    t.g.y = w.ctuY + cs.y;
+    t.sbCols = 1 << (t.g.lw - 2);
+    t.sx = (t.local & (t.sbCols - 1)) << 2;
+    t.sy = (t.local >> (t.g.lw - 2)) << 2;
+  }
+  t.leader = t.myCu >= 0 && (t.lane & ((1 << logNsb) - 1)) == (1 << logNsb) - 1;
+}
+
 // The next task's CU slots into this task's (lane li < kTaskCu of the
 // workgroup or of the wave copies slot li to dstBase + li): reads and writes
 // s_cu.  Cooperative: after every wave's last read of them; autonomous: the
@@ -870,12 +912,14 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
     // it and held in spill slots, whose writes reached HBM
     int tidTask = tidItem;
     opaque(tidTask);
-    const TaskCtx t = task_lanes<KIND>(w, tidTask, coop, s_cu);
-    // the task's values under the names the loop's statements use
-    const int tid = t.tid, lane = t.lane, wv = t.wv, cuB = t.cuB, logS = t.logS, nCuW = t.nCuW;
-    const int myCu = t.myCu, local = t.local, sbIdx = t.sbIdx, sx = t.sx, sy = t.sy, sbCols = t.sbCols;
-    const bool active = t.active, leader = t.leader;
-    const Geo g = t.g;
+    TaskCtx t = task_lanes<KIND>(w, tidTask, coop, s_cu);
+    // the task's values under the names the loop's statements use (the lane's
+    // place in the task changes only at a hand-over, see relayout_task)
+    const int tid = t.tid, lane = t.lane, wv = t.wv, cuB = t.cuB, nCuW = t.nCuW;
+    int sbIdx = t.sbIdx, logS = t.logS, myCu = t.myCu, local = t.local, sx = t.sx, sy = t.sy, sbCols = t.sbCols;
+    bool active = t.active, leader = t.leader;
+    Geo g = t.g;
+    [[maybe_unused]] const int pcLogS = t.logS;  // (the prediction counters)
     // one copy of the pass per CP count and item class: ncp and coop are
     // compile-time constants in each, so the 2-CP pass carries none of the 3-CP
     // selects and branches, and each copy keeps its spills outside its loops
@@ -887,6 +931,16 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
       (void)ph_off;
       constexpr int kDup = (VAME_DUP & 32) && ncp != 3 ? 0 : VAME_DUP;  // timing-only builds
       const int niter = (ncp == 3 ? 4 : 5) + p.extra;
+      // The hand-over (2-CP-only launches' two-sub-block quadrant tasks): once
+      // the task's live CUs hold <= 64 sub-blocks the wave finishes the task
+      // one sub-block per lane (relayout_task) -- one prediction, rows and
+      // gradient pass per iteration instead of two half-empty ones.  Nothing
+      // per lane outlives an iteration but its place in the task: the CU state,
+      // the moments and the system are in LDS, the predictions are formed anew
+      // from the tile and the equation sums are exact integers, so the
+      // results do not depend on the layout.
+      constexpr bool kRelay = VAME_RELAYOUT && KIND == kKindQuad2 && MODE == 1 && ncp == 2 && !coop;
+      [[maybe_unused]] bool relaid = false;  // wave-uniform: this task runs one sub-block per lane
 
       // ---- per-CU initial CPMVs (2 CP: zero; 3 CP: derived from the 2-CP winner)
       if (lane < nCuW) {
@@ -965,6 +1019,11 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
         // 3-CP iteration 0 of a seed-reuse CU: SATD (set at init) and gradient
         // sums come from the 2-CP pass
         const bool reuse = ncp == 3 && iter == 0 && s_st[myCu < 0 ? 0 : myCu].seedSkip;
+#if VAME_COUNT_PRED
+        if constexpr (KIND == kKindQuad2 && ncp == 2) {
+          if (!coop && pcLogS < 6) PC2_ITER(__builtin_amdgcn_ballot_w64(live), relaid ? 1u : 2u, iter)
+        }
+#endif
         if (live && !reuse && !(VAME_ABLATE & 8)) {
           PC_ADD
           Geo gp = g;
@@ -989,6 +1048,7 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
           int satdLane = 0;
 #pragma unroll
           for (int j = 0; j < SBL; j++) {
+            if (kRelay && j > 0 && relaid) break;  // uniform: one sub-block per lane
             bool outside;
             satdLane += predict_sb<C::TILE, C::TP, PROF, (VAME_ABLATE & 1024) != 0 && ncp == 3, ncp>(
                 f, sxp, syp + 4 * j, gp, s_tile, tx0, ty0, tileW - 9, tileH - 9, ref, cur, W, H, s_coef, Pr[j],
@@ -1020,7 +1080,12 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
           // extended rows (neighbour columns by DPP), edge rows published for
           // the sub-blocks above and below (SBL = 2: the gradient step forms
           // the extended rows of both sub-blocks)
-          publish_rows<SBL>(Pr, sbIdx, s_top, s_bot, X);
+          if (kRelay && relaid) {  // the one sub-block's own top and bottom row
+            s_top[sbIdx] = Pr[0][0];
+            s_bot[sbIdx] = Pr[0][3];
+          } else {
+            publish_rows<SBL>(Pr, sbIdx, s_top, s_bot, X);
+          }
           if constexpr ((kDup & 256) != 0) {  // timing-only: the extended rows and edge stores again
             int i2 = sbIdx;
             opaque(i2);
@@ -1174,7 +1239,8 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
 #pragma unroll
                 for (int r = 0; r < 4; r++)
                   X[r + 1] = ext_row_dpp(Pr[j][r]);
-                X[5] = ext_row_dpp(j + 1 < SBL ? Pr[j + 1][0] : bt);
+                const bool below = j + 1 < SBL && !(kRelay && relaid);  // the row below is the lane's own
+                X[5] = ext_row_dpp(below ? Pr[j + 1 < SBL ? j + 1 : j][0] : bt);
                 {
                   const unsigned b0 = (unsigned)((gg.y + syg + 4 * j) * W + gg.x + sxg) * 2u, bw = (unsigned)W * 2u;
                   const char* base = reinterpret_cast<const char*>(cur);
@@ -1182,6 +1248,7 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
                   for (int r = 0; r < 4; r++) Og[j][r] = *reinterpret_cast<const uint2*>(base + (b0 + (unsigned)r * bw));
                 }
                 grad_sb(sxg, syg + 4 * j, gg, X, Og[j], S[j]);
+                if (kRelay && relaid) break;  // uniform: one sub-block per lane
                 if (j + 1 < SBL) X[0] = X[4];  // the lower sub-block's row above = the upper one's row 3
               }
             }
@@ -1210,7 +1277,12 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
             int va[SBL];
 #pragma unroll
             for (int j = 0; j < SBL; j++) va[j] = sy + 2 + 4 * j;
-            if (ncp == 2)
+            if (kRelay && relaid) {  // the one sub-block's values alone
+              int S1[1][5], v1[1] = {va[0]};
+#pragma unroll
+              for (int k = 0; k < 5; k++) S1[0][k] = S[0][k];
+              reduce_equations<2, 1>(S1, sx + 2, v1, logS, myCu >= 0, coop, dst);
+            } else if (ncp == 2)
               reduce_equations<2, SBL>(S, sx + 2, va, logS, myCu >= 0, coop, dst);
             else
               reduce_equations<3, SBL>(S, sx + 2, va, logS, myCu >= 0, coop, dst);
@@ -1232,9 +1304,23 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
         if (!(VAME_ABLATE & 1)) {
           const bool liveNew = solve_update_phase<ncp, coop, keepS, kDup>(w, t, s_cu, s_st, s_val, s_mat, s_eqmap);
           if (!coop) {
-            if (__ballot(liveNew) == 0) {
+            const unsigned long long liveBal = __ballot(liveNew);  // lane 7 of every CU that stays live
+            if (liveBal == 0) {
               __builtin_amdgcn_s_setprio(0);
               break;
+            }
+            if constexpr (kRelay) {
+              // the hand-over: CUs of 32 or 64 sub-blocks (16 or 32 lanes each so
+              // far), not handed over yet, the live ones fitting the wave's lanes
+              if (!relaid && t.logL < 6 && (__popcll(liveBal) << (t.logL + 1)) <= 64) {
+                unsigned liveCus = 0;
+                for (int k = 0; k < (64 >> t.logL); k++)
+                  liveCus |= (unsigned)((liveBal >> ((k << t.logL) + 7)) & 1) << k;
+                relayout_task(w, liveCus, s_cu, t);
+                sbIdx = t.sbIdx; logS = t.logS; myCu = t.myCu; local = t.local; sx = t.sx; sy = t.sy; sbCols = t.sbCols;
+                active = t.active; leader = t.leader; g = t.g;
+                relaid = true;
+              }
             }
           }
         }
@@ -1276,6 +1362,13 @@ __device__ __forceinline__ void affine_me_body(const KParams& p, L& lds) {
     if (coop) {
       take_task_slots<KIND>(next, tid, 0, s_cu);
       __syncthreads();
+    } else if constexpr (VAME_RELAYOUT && KIND == kKindQuad2 && MODE == 1) {
+      // the wave's slot base re-derived (opaque): carried from the task's
+      // start past the hand-over's code it took a spill slot
+      int tidEnd = tidItem;
+      opaque(tidEnd);
+      take_task_slots<KIND>(next, tidEnd & 63, (tidEnd >> 6) * kTaskCu, s_cu);
+      wave_sync();
     } else {
       take_task_slots<KIND>(next, lane, wv * kTaskCu, s_cu);
       wave_sync();

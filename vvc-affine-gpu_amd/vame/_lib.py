@@ -28,6 +28,14 @@ EXPORTS = (
 )
 
 
+# the facts of include/vame.h the package computes with; every module imports them from here
+MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")  # PRED m: alignment m >> 1, 2-CP | 3-CP m & 1
+CUS_PER_CTU = (201, 284)  # candidate CUs per CTU of the FULL / HALF alignment (vame_cus_per_ctu)
+MAX_PENALTY = 1 << 40  # largest split / bi penalty of vame_partition(_bi)
+# mode_mask bits: 2-CP, 3-CP, and the alignment selection
+MODE_2CP, MODE_3CP, MODE_FULL, MODE_HALF = 1, 2, 4, 8
+
+
 class VameError(RuntimeError):
     pass
 

@@ -6,14 +6,14 @@ from __future__ import annotations
 
 import torch
 
+from ._lib import CUS_PER_CTU, MAX_PENALTY, MODES  # noqa: F401  (MAX_PENALTY: re-exported)
 from .mc import CU_FIELDS, candidate_geometry
+from .partition import alloc_keys, keys_to_host
 
 # vame_mc_bicu: a vame_mc_cu, then ref1 (-1: uni-predicted) and the second hypothesis
 BICU_FIELDS = CU_FIELDS[:4] + ("ref0", "nCPs0", "LTx0", "LTy0", "RTx0", "RTy0", "LBx0", "LBy0",
                                "ref1", "nCPs1", "LTx1", "LTy1", "RTx1", "RTy1", "LBx1", "LBy1")
-MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
 KEYS = ("cus", "rows", "sel", "ncus", "ctu_info", "ctu_cost", "block_cu")
-MAX_PENALTY = 1 << 40
 NONE_COST = (1 << 63) - 1  # bi_cost of a row without a pair
 
 
@@ -74,26 +74,16 @@ def bicus_from_sel(W: int, H: int, align: int, result: dict, sel: torch.Tensor, 
 
 def alloc(n_ctus: int, device) -> dict:
     """The outputs of vame_partition_bi."""
-    i32 = dict(dtype=torch.int32, device=device)
-    return {"cus": torch.empty((n_ctus * 64, 20), **i32), "rows": torch.empty(n_ctus * 64, **i32),
-            "sel": torch.empty(n_ctus * 64, **i32), "ncus": torch.empty((), **i32),
-            "ctu_info": torch.empty((n_ctus, 4), **i32),
-            "ctu_cost": torch.empty(n_ctus, dtype=torch.int64, device=device),
-            "block_cu": torch.empty(n_ctus * 64, **i32)}
+    return alloc_keys(KEYS, 20, n_ctus, device)
 
 
 def alloc_bi(n_ctus: int, device) -> dict:
     """The outputs of vame_bipred: {"cost": [FULL, HALF], "sel": [FULL, HALF]}."""
-    return {"cost": [torch.empty(n_ctus * per, dtype=torch.int64, device=device) for per in (201, 284)],
-            "sel": [torch.empty(n_ctus * per, dtype=torch.int32, device=device) for per in (201, 284)]}
+    return {"cost": [torch.empty(n_ctus * per, dtype=torch.int64, device=device) for per in CUS_PER_CTU],
+            "sel": [torch.empty(n_ctus * per, dtype=torch.int32, device=device) for per in CUS_PER_CTU]}
 
 
 def to_host(part: dict) -> dict:
     """The outputs as numpy arrays, cus, rows and sel cut at the leaf count
     (synchronizes: reads the count)."""
-    n = int(part["ncus"])
-    out = {k: part[k].cpu().numpy() for k in KEYS}
-    for k in ("cus", "rows", "sel"):
-        out[k] = out[k][:n]
-    out["ncus"] = n
-    return out
+    return keys_to_host(KEYS, part)

@@ -16,12 +16,12 @@ import ctypes
 
 import torch
 
-from ._lib import Mvp, PocJob, PocResult, SeedResult, check, lib
+from . import bipred as B
+from . import partition as P
+from ._lib import (CUS_PER_CTU, MAX_PENALTY, MODE_2CP, MODE_3CP, MODE_FULL, MODE_HALF, MODES,  # noqa: F401
+                   Mvp, PocJob, PocResult, SeedResult, check, lib)
 
 CPMV_FIELDS = ("nCPs", "LTx", "LTy", "RTx", "RTy", "LBx", "LBy")
-MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
-# mode_mask bits (include/vame.h): 2-CP, 3-CP, and the alignment selection
-MODE_2CP, MODE_3CP, MODE_FULL, MODE_HALF = 1, 2, 4, 8
 
 
 def pred_mask(modes: int) -> int:
@@ -103,7 +103,7 @@ class Engine:
         return t.value, n.value
 
     def n_cus(self, align: int) -> int:
-        return self.n_ctus * (284 if align else 201)
+        return self.n_ctus * CUS_PER_CTU[bool(align)]
 
     def _frame(self, f: torch.Tensor) -> torch.Tensor:
         if f.shape != (self.H, self.W) or f.device != self.device or f.dtype not in (torch.int16, torch.uint16):
@@ -137,19 +137,24 @@ class Engine:
         if t is not None and (t.numel() != 1 or t.dtype != torch.int32 or t.device != self.device):
             raise ValueError(f"{name} must be an int32 scalar on {self.device}")
 
-    def _check_part_out(self, out: dict, want: dict, cols: int) -> None:
-        """The tensors of a partition() (cols = 12) / partition_bi() (20) result
-        to write into: `want` holds the dtype of every key."""
-        shapes = {"cus": (self.n_ctus * 64, cols), "ctu_info": (self.n_ctus, 4), "ncus": (),
-                  "ctu_cost": (self.n_ctus,)}
-        for k, w in want.items():
-            t, shape = out[k], shapes.get(k, (self.n_ctus * 64,))
-            if tuple(t.shape) != shape or t.dtype != w.dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"out[{k!r}] must be a contiguous {w.dtype} {shape} tensor on {self.device}")
+    def _bad(self) -> torch.Tensor:
+        """A cleared `bad` flag: the int32 device scalar the kernels OR into."""
+        return torch.zeros((), dtype=torch.int32, device=self.device)
 
-    def _mc_checks(self, what: str, cols: int, cus, refs, cur, pred, want_cost: bool, ncus):
-        """The argument checks of affine_mc (cols = 12) and affine_mc_bi (20), in
-        their order: (cur or None, the reference pointers, nrefs)."""
+    @staticmethod
+    def _preds(result: dict, preds: int | None, full: bool = False) -> int:
+        """The PRED mask of a call on an alloc_poc dict: `preds`, or every PRED
+        the dict holds; at least one PRED, with `full` a FULL one."""
+        preds = P.result_preds(result) if preds is None else int(preds)
+        if preds & ~15 or not preds & (3 if full else 15):
+            raise ValueError(f"preds must hold a {'FULL PRED (bit 0 or 1)' if full else 'PRED'} and only bits 0..3")
+        return preds
+
+    def _mc(self, what: str, cols: int, cus, refs, lam: float, cur, pred, want_cost: bool, ncus):
+        """What affine_mc (cols = 12), affine_mc_bi and affine_mc_p (20) share
+        around their C call: the argument checks and the cost / bad buffers.
+        Returns the call's leading arguments up to cus, its trailing ones from
+        lambda on, and the (pred, cost, bad) to return."""
         self._check_cus(cus, cols)
         if pred is None and not want_cost:
             raise ValueError(f"{what} needs pred, want_cost or both")
@@ -160,7 +165,31 @@ class Engine:
             cur = self._frame(cur)
         self._check_pred(pred)
         self._check_scalar(ncus, "ncus")
-        return cur if want_cost else None, ref_ptrs, len(refs)
+        cost = torch.empty(cus.shape[0], dtype=torch.int64, device=self.device) if want_cost else None
+        bad = self._bad()
+        return ((self._h, _ptr(cur if want_cost else None), ref_ptrs, len(refs), _ptr(cus)),
+                (float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()), (pred, cost, bad))
+
+    def _refine(self, plain, with_preds, cols: int, per: int, it_name: str, it_max: int, cus, preds, refs, cur,
+                lam: float, iters: int, count, out, cost):
+        """affine_search(_p) and bipred_refine(_p), parametrised as the C side's
+        refine_cus: descriptors of `cols` columns with `per` predictor rows
+        each, `iters` (called `it_name`) in 0..it_max.  Calls the symbol
+        `plain` without preds, `with_preds` with them."""
+        self._check_cus(cus, cols)
+        if not 0 <= int(iters) <= it_max:
+            raise ValueError(f"{it_name} must be in 0..{it_max}")
+        refs, ref_ptrs = self._refs(refs, plain.__name__)
+        cur = self._frame(cur)
+        n = cus.shape[0]
+        self._check_preds(preds, per * n, with_preds.__name__)
+        self._check_scalar(count, "the descriptor count")
+        out, cost = self._refine_out(cus, out, cost)
+        bad = self._bad()
+        head = (self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus))
+        tail = (n, _ptr(count), float(lam), int(iters), _ptr(out), _ptr(cost), _ptr(bad), self._stream())
+        check(plain(*head, *tail) if preds is None else with_preds(*head, _ptr(preds), *tail))
+        return out, cost, bad
 
     def _refine_out(self, cus: torch.Tensor, out, cost):
         """The out / cost buffers of affine_search and bipred_refine for the
@@ -237,10 +266,9 @@ class Engine:
         arr = (PocJob * len(jobs))()
         for j, (cur, refs, lam, out) in enumerate(jobs):
             cur = self._frame(cur)
-            refs = [self._frame(r) for r in refs]
+            refs, ref_ptrs = self._refs(refs, "affine_me_batch")
             self._check_poc_out(out, len(refs), modes)
             pr = _poc_result(out)
-            ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
             keep += [cur, refs, pr, ref_ptrs]
             arr[j].cur = cur.data_ptr()
             arr[j].refs = ctypes.cast(ref_ptrs, ctypes.c_void_p)
@@ -264,7 +292,7 @@ class Engine:
             raise ValueError("slab larger than the agreed size")
         slab = torch.empty(words, dtype=torch.int32, device=self.device)
         if bad is None:
-            bad = torch.zeros((), dtype=torch.int32, device=self.device)
+            bad = self._bad()
         arr = (PocJob * max(len(results), 1))()
         keep = []
         for j, res in enumerate(results):
@@ -293,17 +321,12 @@ class Engine:
         number of descriptors to run (vame_affine_mc_dev: min(ncus, n), read on
         the device; rows of cus and cost past it are neither read nor
         written).  Asynchronous on the current stream."""
-        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc", 12, cus, refs, cur, pred, want_cost, ncus)
-        n = cus.shape[0]
-        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        head, tail, ret = self._mc("affine_mc", 12, cus, refs, lam, cur, pred, want_cost, ncus)
         if ncus is not None:
-            check(lib().vame_affine_mc_dev(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, _ptr(ncus), float(lam),
-                                           _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
+            check(lib().vame_affine_mc_dev(*head, cus.shape[0], _ptr(ncus), *tail))
         else:
-            check(lib().vame_affine_mc(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, float(lam), _ptr(pred),
-                                       _ptr(cost), _ptr(bad), self._stream()))
-        return pred, cost, bad
+            check(lib().vame_affine_mc(*head, cus.shape[0], *tail))
+        return ret
 
     def partition(self, result: dict, preds: int | None = None, split_penalty: int = 0, out: dict | None = None):
         """vame_partition: per CTU the cheapest tiling by the candidate CUs of
@@ -318,25 +341,31 @@ class Engine:
         count, holes, splits), ctu_cost int64 [nCtus], block_cu int32
         [nCtus*64].  out: a dict of an earlier call to write into.  Reads
         nothing on the host; asynchronous on the current stream."""
-        from . import partition as P
-        if not result:
-            raise ValueError("partition needs a result dict")
-        have = P.result_preds(result)
-        preds = have if preds is None else int(preds)
-        nrefs = max(r for r, _ in result) + 1
-        if preds & ~15 or not preds & 3:
-            raise ValueError("preds must hold a FULL PRED (bit 0 or 1) and only bits 0..3")
-        if not 0 <= int(split_penalty) <= P.MAX_PENALTY:
-            raise ValueError("split_penalty must be in [0, 2^40]")
-        for r in range(nrefs):
-            for m, name in enumerate(MODES):
-                if (preds >> m) & 1:
-                    if (r, name) not in result:
-                        raise ValueError(f"result buffers missing for {(r, name)}")
-                    self._check_out(result[(r, name)], m >> 1)
-        if out is not None:
-            self._check_part_out(out, P.alloc(0, "cpu"), 12)
-        return P.partition(self._h, self.n_ctus, self.device, result, preds, split_penalty, self._stream(), out)
+        return self._partition(P, result, None, preds, split_penalty, 0, out)
+
+    def _partition(self, form, result: dict, bi, preds, split_penalty: int, bi_penalty: int, out: dict | None):
+        """partition() (form = vame.partition, which names its outputs) and
+        partition_bi() (form = vame.bipred, with the bi arrays)."""
+        what = "partition" if form is P else "partition_bi"
+        preds = self._preds(result, preds, full=True)
+        if not 0 <= int(split_penalty) <= MAX_PENALTY or not 0 <= int(bi_penalty) <= MAX_PENALTY:
+            raise ValueError("split_penalty and bi_penalty must be in [0, 2^40]")
+        nrefs, pr = self._check_result(result, preds, what)
+        if form is B:
+            bcost, bsel = self._check_bi(bi, preds)
+        if out is None:
+            out = form.alloc(self.n_ctus, self.device)
+        for k, w in form.alloc(self.n_ctus, "meta").items():
+            t = out[k]
+            if t.shape != w.shape or t.dtype != w.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {w.dtype} {tuple(w.shape)} tensor on {self.device}")
+        head = (self._h, ctypes.byref(pr), nrefs, preds, int(split_penalty))
+        ptrs = [_ptr(out[k]) for k in form.KEYS]
+        if form is P:
+            check(lib().vame_partition(*head, *ptrs, self._stream()))
+        else:
+            check(lib().vame_partition_bi(*head, bcost, bsel, int(bi_penalty), *ptrs, self._stream()))
+        return out
 
     def predict_partition(self, part: dict, refs, lam: float = 0.0, cur: torch.Tensor | None = None,
                           pred: torch.Tensor | None = None, want_cost: bool = False):
@@ -349,14 +378,17 @@ class Engine:
         return self.affine_mc(part["cus"], refs, lam, cur=cur, pred=pred, want_cost=want_cost, ncus=part["ncus"])
 
     # ---- bi-prediction
-    def _check_result(self, result: dict, preds: int, what: str):
+    def _check_result(self, result: dict, preds: int, what: str, refs=None):
         """An alloc_poc dict that holds every PRED of `preds` for refIdx
-        0 .. nrefs-1: (nrefs, its vame_poc_result)."""
+        0 .. nrefs-1, over the frames `refs` where given: (nrefs, its
+        vame_poc_result)."""
         if not result:
             raise ValueError(f"{what} needs a result dict")
         nrefs = max(r for r, _ in result) + 1
         if not 1 <= nrefs <= 4:
             raise ValueError(f"{what} takes the results of 1..4 references")
+        if refs is not None and nrefs != len(refs):
+            raise ValueError(f"{what}: the result dict holds {nrefs} references, refs {len(refs)}")
         need = {}
         for r in range(nrefs):
             for m, name in enumerate(MODES):
@@ -394,13 +426,18 @@ class Engine:
         exactly affine_mc; else the sample is the once-rounded average of the
         two hypotheses and the cost carries both rates.  Arguments and the
         returned (pred, cost, bad) as affine_mc.  Not available under PROF."""
-        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc_bi", 20, cus, refs, cur, pred, want_cost, ncus)
+        return self._mc_bi("affine_mc_bi", cus, None, refs, lam, cur, pred, want_cost, ncus)
+
+    def _mc_bi(self, what: str, cus, preds, refs, lam: float, cur, pred, want_cost: bool, ncus):
+        """affine_mc_bi, and with `preds` (int32 [2n, 7]) affine_mc_p."""
+        head, tail, ret = self._mc(what, 20, cus, refs, lam, cur, pred, want_cost, ncus)
         n = cus.shape[0]
-        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_mc_bi(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), n, _ptr(ncus), float(lam),
-                                      _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
-        return pred, cost, bad
+        self._check_preds(preds, 2 * n, what)
+        if preds is None:
+            check(lib().vame_affine_mc_bi(*head, n, _ptr(ncus), *tail))
+        else:
+            check(lib().vame_affine_mc_bi_p(*head, _ptr(preds), n, _ptr(ncus), *tail))
+        return ret
 
     def bipred(self, cur, refs, lam: float, result: dict, preds: int | None = None, out: dict | None = None):
         """vame_bipred: for every candidate CU of `result` (an alloc_poc dict
@@ -411,24 +448,24 @@ class Engine:
         row with one reference, hold INT64_MAX and -1; sel = r0 + 4*m0 + 8*r1 +
         32*m1 (vame.bipred.decode_sel).  preds: None = every PRED the dict
         holds.  out: a dict of an earlier call to write into."""
-        from . import bipred as B
-        from . import partition as P
+        return self._bipred("bipred", cur, refs, lam, result, None, preds, out)
+
+    def _bipred(self, what: str, cur, refs, lam: float, result: dict, mvp: dict | None, preds, out: dict | None):
+        """bipred, and with `mvp` bipred_p."""
         cur = self._frame(cur)
-        refs, ref_ptrs = self._refs(refs, "bipred")
-        if not result:
-            raise ValueError("bipred needs a result dict")
-        preds = P.result_preds(result) if preds is None else int(preds)
-        if preds & ~15 or not preds:
-            raise ValueError("preds must hold a PRED and only bits 0..3")
-        nrefs, pr = self._check_result(result, preds, "bipred")
-        if nrefs != len(refs):
-            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
+        refs, ref_ptrs = self._refs(refs, what)
+        preds = self._preds(result, preds)
+        nrefs, pr = self._check_result(result, preds, what, refs)
+        m = None if mvp is None else self._mv_table(mvp, nrefs, preds, f"{what}: mvp")
         if out is None:
             full = B.alloc_bi(self.n_ctus, self.device)
             out = {k: [t if (preds >> (2 * a)) & 3 else None for a, t in enumerate(full[k])] for k in ("cost", "sel")}
         cost, sel = self._check_bi(out, preds)
-        check(lib().vame_bipred(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds,
-                                cost, sel, self._stream()))
+        head = (self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds)
+        if m is None:
+            check(lib().vame_bipred(*head, cost, sel, self._stream()))
+        else:
+            check(lib().vame_bipred_p(*head, ctypes.byref(m), cost, sel, self._stream()))
         return out
 
     def partition_bi(self, result: dict, bi: dict, preds: int | None = None, split_penalty: int = 0,
@@ -438,24 +475,7 @@ class Engine:
         (bi: a bipred() result over the same `result`).  Returns the tensors of
         partition() with cus int32 [nCtus*64, 20] (vame.bipred.BICU_FIELDS;
         ref1 = -1 for a uni leaf) and sel int32 [nCtus*64] (bi_sel, or -1)."""
-        from . import bipred as B
-        from . import partition as P
-        if not result:
-            raise ValueError("partition_bi needs a result dict")
-        preds = P.result_preds(result) if preds is None else int(preds)
-        if preds & ~15 or not preds & 3:
-            raise ValueError("preds must hold a FULL PRED (bit 0 or 1) and only bits 0..3")
-        if not 0 <= int(split_penalty) <= B.MAX_PENALTY or not 0 <= int(bi_penalty) <= B.MAX_PENALTY:
-            raise ValueError("split_penalty and bi_penalty must be in [0, 2^40]")
-        nrefs, pr = self._check_result(result, preds, "partition_bi")
-        bcost, bsel = self._check_bi(bi, preds)
-        if out is None:
-            out = B.alloc(self.n_ctus, self.device)
-        self._check_part_out(out, B.alloc(0, "cpu"), 20)
-        V = ctypes.c_void_p
-        check(lib().vame_partition_bi(self._h, ctypes.byref(pr), nrefs, preds, int(split_penalty), bcost, bsel,
-                                      int(bi_penalty), *(V(out[k].data_ptr()) for k in B.KEYS), self._stream()))
-        return out
+        return self._partition(B, result, bi, preds, split_penalty, bi_penalty, out)
 
     # ---- refinement of bi-predicted CUs (DESIGN.md section 14)
     def bipred_refine(self, cus: torch.Tensor, refs, cur, lam: float, rounds: int = 2,
@@ -472,18 +492,7 @@ class Engine:
         an int32 scalar on the device, the number of descriptors to work on
         (entries past it stay untouched); out may be cus.  Reads nothing on the
         host; asynchronous on the current stream.  Not available under PROF."""
-        self._check_cus(cus, 20)
-        if not 0 <= int(rounds) <= 4:
-            raise ValueError("rounds must be in 0..4")
-        refs, ref_ptrs = self._refs(refs, "bipred_refine")
-        cur = self._frame(cur)
-        n = cus.shape[0]
-        self._check_scalar(count, "count")
-        out, cost = self._refine_out(cus, out, cost)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_bipred_refine(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(count),
-                                       float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
-        return out, cost, bad
+        return self.bipred_refine_p(cus, None, refs, cur, lam, rounds, count, out, cost)
 
     def refine_partition(self, part: dict, refs, cur, lam: float, rounds: int = 2) -> dict:
         """bipred_refine on the leaves of a partition_bi() result, their count
@@ -509,11 +518,7 @@ class Engine:
         with the same `rounds` turns them into the descriptors refined here, at
         the costs the partition used.  `bi` is not modified.  Reads the
         selection on the host (synchronizes)."""
-        from . import bipred as B
-        from . import partition as P
-        preds = P.result_preds(result) if preds is None else int(preds)
-        if preds & ~15 or not preds:
-            raise ValueError("preds must hold a PRED and only bits 0..3")
+        preds = self._preds(result, preds)
         self._check_result(result, preds, "refine_bipred")
         self._check_bi(bi, preds)
         out = {"cost": [None, None], "sel": [None, None], "cus": [None, None], "rows": [None, None]}
@@ -643,18 +648,7 @@ class Engine:
         the device, the number of descriptors to work on (entries past it stay
         untouched); out may be cus.  Reads nothing on the host; asynchronous on
         the current stream.  Not available under PROF."""
-        self._check_cus(cus, 12)
-        if not 0 <= int(extra) <= 64:
-            raise ValueError("extra must be in 0..64")
-        refs, ref_ptrs = self._refs(refs, "affine_search")
-        cur = self._frame(cur)
-        n = cus.shape[0]
-        self._check_scalar(ncus, "ncus")
-        out, cost = self._refine_out(cus, out, cost)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_search(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), n, _ptr(ncus), float(lam),
-                                       int(extra), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
-        return out, cost, bad
+        return self.affine_search_p(cus, None, refs, cur, lam, extra, ncus, out, cost)
 
     def affine_me_seeded(self, cur, refs, lam: float, result: dict, seeds: dict, modes: int = 3, extra: int = 0):
         """vame_affine_me_seeded: improve `result` (the alloc_poc dict
@@ -667,28 +661,31 @@ class Engine:
         a seed was out of range (its row is skipped).  torch allocates the work
         buffer.  Reads nothing on the host; asynchronous on the current stream.
         Not available under PROF."""
+        return self._seeded("affine_me_seeded", cur, refs, lam, result, seeds, None, modes, extra)
+
+    def _seeded(self, what: str, cur, refs, lam: float, result: dict, seeds: dict, mvp: dict | None, modes: int,
+                extra: int):
+        """affine_me_seeded, and with `mvp` affine_me_seeded_p."""
         cur = self._frame(cur)
-        refs, ref_ptrs = self._refs(refs, "affine_me_seeded")
+        refs, ref_ptrs = self._refs(refs, what)
         if not int(modes) & MODE_2CP or int(modes) & ~15:
             raise ValueError("modes must hold MODE_2CP and only bits 0..3")
         if not 0 <= int(extra) <= 64:
             raise ValueError("extra must be in 0..64")
         preds = pred_mask(modes)
-        nrefs, pr = self._check_result(result, preds, "affine_me_seeded")
-        if nrefs != len(refs):
-            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
-        ptrs = ((ctypes.c_void_p * 2) * 4)()
-        for r in range(nrefs):
-            for a in (0, 1):
-                if (preds >> (2 * a)) & 3:
-                    t = seeds.get((r, a)) if isinstance(seeds, dict) else None
-                    ptrs[r][a] = self._check_seed(t, a, f"seeds[{(r, a)}]", torch.int32, (2,)).data_ptr()
-        nbytes = lib().vame_seeded_work_bytes(self._h, nrefs, int(modes))
+        nrefs, pr = self._check_result(result, preds, what, refs)
+        s = self._mv_table(seeds, nrefs, preds, f"{what}: seeds")
+        m = None if mvp is None else self._mv_table(mvp, nrefs, preds, f"{what}: mvp")
+        L = lib()
+        nbytes = (L.vame_seeded_work_bytes if m is None else L.vame_seeded_p_work_bytes)(self._h, nrefs, int(modes))
         work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_me_seeded(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), int(modes), int(extra),
-                                          ptrs, ctypes.byref(pr), _ptr(work), work.numel() * 8, _ptr(bad),
-                                          self._stream()))
+        bad = self._bad()
+        head = (self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), int(modes), int(extra), s.mv)
+        tail = (ctypes.byref(pr), _ptr(work), work.numel() * 8, _ptr(bad), self._stream())
+        if m is None:
+            check(L.vame_affine_me_seeded(*head, *tail))
+        else:
+            check(L.vame_affine_me_seeded_p(*head, ctypes.byref(m), *tail))
         return result, bad
 
     # ---- rates against a motion-vector predictor (DESIGN.md section 17)
@@ -699,16 +696,30 @@ class Engine:
                                   or preds.device != self.device or not preds.is_contiguous()):
             raise ValueError(f"{what}: preds must be a contiguous int32 [{n}, 7] tensor on {self.device}")
 
-    def _mvp(self, mvp: dict, nrefs: int, preds: int, what: str) -> Mvp:
+    def _mv_table(self, mvs: dict, nrefs: int, preds: int, what: str) -> Mvp:
         """{(r, a): int32 [n, 2]} (seed_search()["mv"], region_predictors()) as a
-        vame_mvp: every (r, alignment) with a PRED in `preds` must be there."""
+        vame_mvp, whose .mv is the [4][2] pointer table the seeds travel in:
+        every (r, alignment) with a PRED in `preds` must be there."""
         out = Mvp()
         for r in range(nrefs):
             for a in (0, 1):
                 if (preds >> (2 * a)) & 3:
-                    t = mvp.get((r, a)) if isinstance(mvp, dict) else None
-                    out.mv[r][a] = self._check_seed(t, a, f"{what}: mvp[{(r, a)}]", torch.int32, (2,)).data_ptr()
+                    t = mvs.get((r, a)) if isinstance(mvs, dict) else None
+                    out.mv[r][a] = self._check_seed(t, a, f"{what}[{(r, a)}]", torch.int32, (2,)).data_ptr()
         return out
+
+    @staticmethod
+    def _widen(cus: torch.Tensor, preds: torch.Tensor | None = None):
+        """Uni descriptors [n, 12] as uni bi descriptors [n, 20] (ref1 = -1), and
+        their predictors [n, 7] at the rows 2i of a [2n, 7] tensor."""
+        wide = torch.zeros((cus.shape[0], 20), dtype=torch.int32, device=cus.device)
+        wide[:, :12] = cus
+        wide[:, 12] = -1
+        if preds is not None:
+            p2 = torch.zeros((cus.shape[0], 2, 7), dtype=torch.int32, device=cus.device)
+            p2[:, 0] = preds
+            preds = p2.reshape(-1, 7)
+        return wide, preds
 
     def affine_mc_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, lam: float = 0.0,
                     cur: torch.Tensor | None = None, pred: torch.Tensor | None = None, want_cost: bool = False,
@@ -727,22 +738,8 @@ class Engine:
         if cus.dim() == 2 and cus.shape[1] == 12:
             self._check_cus(cus, 12)
             self._check_preds(preds, cus.shape[0], "affine_mc_p")
-            wide = torch.zeros((cus.shape[0], 20), dtype=torch.int32, device=self.device)
-            wide[:, :12] = cus
-            wide[:, 12] = -1
-            if preds is not None:
-                p2 = torch.zeros((cus.shape[0], 2, 7), dtype=torch.int32, device=self.device)
-                p2[:, 0] = preds
-                preds = p2.reshape(-1, 7)
-            cus = wide
-        cur, ref_ptrs, nrefs = self._mc_checks("affine_mc_p", 20, cus, refs, cur, pred, want_cost, ncus)
-        n = cus.shape[0]
-        self._check_preds(preds, 2 * n, "affine_mc_p")
-        cost = torch.empty(n, dtype=torch.int64, device=self.device) if want_cost else None
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_mc_bi_p(self._h, _ptr(cur), ref_ptrs, nrefs, _ptr(cus), _ptr(preds), n, _ptr(ncus),
-                                        float(lam), _ptr(pred), _ptr(cost), _ptr(bad), self._stream()))
-        return pred, cost, bad
+            cus, preds = self._widen(cus, preds)
+        return self._mc_bi("affine_mc_p", cus, preds, refs, lam, cur, pred, want_cost, ncus)
 
     def affine_search_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, cur, lam: float, extra: int = 0,
                         ncus: torch.Tensor | None = None, out: torch.Tensor | None = None,
@@ -751,19 +748,9 @@ class Engine:
         taken against preds[i] (int32 [n, 7], as affine_mc_p), so the predictor
         takes part in which iteration wins.  cost is affine_mc_p's cost of out
         with the same predictors.  preds None: affine_search bit for bit."""
-        self._check_cus(cus, 12)
-        if not 0 <= int(extra) <= 64:
-            raise ValueError("extra must be in 0..64")
-        refs, ref_ptrs = self._refs(refs, "affine_search_p")
-        cur = self._frame(cur)
-        n = cus.shape[0]
-        self._check_preds(preds, n, "affine_search_p")
-        self._check_scalar(ncus, "ncus")
-        out, cost = self._refine_out(cus, out, cost)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_search_p(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), _ptr(preds), n, _ptr(ncus),
-                                         float(lam), int(extra), _ptr(out), _ptr(cost), _ptr(bad), self._stream()))
-        return out, cost, bad
+        L = lib()
+        return self._refine(L.vame_affine_search, L.vame_affine_search_p, 12, 1, "extra", 64,
+                            cus, preds, refs, cur, lam, extra, ncus, out, cost)
 
     def bipred_refine_p(self, cus: torch.Tensor, preds: torch.Tensor | None, refs, cur, lam: float, rounds: int = 2,
                         count: torch.Tensor | None = None, out: torch.Tensor | None = None,
@@ -772,20 +759,9 @@ class Engine:
         priced against preds[2i + h] (int32 [2n, 7]) in the start cost and in
         every comparison.  The cost never rises and is affine_mc_p's cost of
         out.  preds None: bipred_refine bit for bit."""
-        self._check_cus(cus, 20)
-        if not 0 <= int(rounds) <= 4:
-            raise ValueError("rounds must be in 0..4")
-        refs, ref_ptrs = self._refs(refs, "bipred_refine_p")
-        cur = self._frame(cur)
-        n = cus.shape[0]
-        self._check_preds(preds, 2 * n, "bipred_refine_p")
-        self._check_scalar(count, "count")
-        out, cost = self._refine_out(cus, out, cost)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_bipred_refine_p(self._h, _ptr(cur), ref_ptrs, len(refs), _ptr(cus), _ptr(preds), n,
-                                         _ptr(count), float(lam), int(rounds), _ptr(out), _ptr(cost), _ptr(bad),
-                                         self._stream()))
-        return out, cost, bad
+        L = lib()
+        return self._refine(L.vame_bipred_refine, L.vame_bipred_refine_p, 20, 2, "rounds", 4,
+                            cus, preds, refs, cur, lam, rounds, count, out, cost)
 
     def reprice(self, lam: float, result: dict, mvp: dict, preds: int | None = None):
         """vame_reprice: replace, in place, the zero-predictor rate in the costs
@@ -795,13 +771,10 @@ class Engine:
         holds).  CPMVs are untouched.  A second call prices twice.  Returns
         (result, bad): bad is 1 when a predictor was out of range (its row is
         skipped).  Pure arithmetic; reads nothing on the host."""
-        from . import partition as P
-        preds = P.result_preds(result) if preds is None else int(preds)
-        if preds & ~15 or not preds:
-            raise ValueError("preds must hold a PRED and only bits 0..3")
+        preds = self._preds(result, preds)
         nrefs, pr = self._check_result(result, preds, "reprice")
-        m = self._mvp(mvp, nrefs, preds, "reprice")
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
+        m = self._mv_table(mvp, nrefs, preds, "reprice: mvp")
+        bad = self._bad()
         check(lib().vame_reprice(self._h, nrefs, float(lam), preds, ctypes.byref(m), ctypes.byref(pr), _ptr(bad),
                                  self._stream()))
         return result, bad
@@ -813,30 +786,9 @@ class Engine:
         re-priced under the same mvp (reprice()).  With an all-zero mvp it is
         affine_me_seeded bit for bit.  Returns (result, bad): bad is 1 when a
         seed or a predictor was out of range (its row is skipped)."""
-        cur = self._frame(cur)
-        refs, ref_ptrs = self._refs(refs, "affine_me_seeded_p")
-        if not int(modes) & MODE_2CP or int(modes) & ~15:
-            raise ValueError("modes must hold MODE_2CP and only bits 0..3")
-        if not 0 <= int(extra) <= 64:
-            raise ValueError("extra must be in 0..64")
-        preds = pred_mask(modes)
-        nrefs, pr = self._check_result(result, preds, "affine_me_seeded_p")
-        if nrefs != len(refs):
-            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
-        ptrs = ((ctypes.c_void_p * 2) * 4)()
-        for r in range(nrefs):
-            for a in (0, 1):
-                if (preds >> (2 * a)) & 3:
-                    t = seeds.get((r, a)) if isinstance(seeds, dict) else None
-                    ptrs[r][a] = self._check_seed(t, a, f"seeds[{(r, a)}]", torch.int32, (2,)).data_ptr()
-        m = self._mvp(mvp, nrefs, preds, "affine_me_seeded_p")
-        nbytes = lib().vame_seeded_p_work_bytes(self._h, nrefs, int(modes))
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
-        bad = torch.zeros((), dtype=torch.int32, device=self.device)
-        check(lib().vame_affine_me_seeded_p(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), int(modes), int(extra),
-                                            ptrs, ctypes.byref(m), ctypes.byref(pr), _ptr(work), work.numel() * 8,
-                                            _ptr(bad), self._stream()))
-        return result, bad
+        if mvp is None:
+            raise ValueError("affine_me_seeded_p needs mvp")
+        return self._seeded("affine_me_seeded_p", cur, refs, lam, result, seeds, mvp, modes, extra)
 
     def bipred_p(self, cur, refs, lam: float, result: dict, mvp: dict, preds: int | None = None,
                  out: dict | None = None):
@@ -845,26 +797,9 @@ class Engine:
         the costs of `result`, which the caller has re-priced (reprice()).  A
         row with a predictor out of range keeps INT64_MAX and -1.  Arguments
         and the returned dict as bipred."""
-        from . import bipred as B
-        from . import partition as P
-        cur = self._frame(cur)
-        refs, ref_ptrs = self._refs(refs, "bipred_p")
-        if not result:
-            raise ValueError("bipred_p needs a result dict")
-        preds = P.result_preds(result) if preds is None else int(preds)
-        if preds & ~15 or not preds:
-            raise ValueError("preds must hold a PRED and only bits 0..3")
-        nrefs, pr = self._check_result(result, preds, "bipred_p")
-        if nrefs != len(refs):
-            raise ValueError(f"the result dict holds {nrefs} references, refs {len(refs)}")
-        m = self._mvp(mvp, nrefs, preds, "bipred_p")
-        if out is None:
-            full = B.alloc_bi(self.n_ctus, self.device)
-            out = {k: [t if (preds >> (2 * a)) & 3 else None for a, t in enumerate(full[k])] for k in ("cost", "sel")}
-        cost, sel = self._check_bi(out, preds)
-        check(lib().vame_bipred_p(self._h, _ptr(cur), ref_ptrs, nrefs, float(lam), ctypes.byref(pr), preds,
-                                  ctypes.byref(m), cost, sel, self._stream()))
-        return out
+        if mvp is None:
+            raise ValueError("bipred_p needs mvp")
+        return self._bipred("bipred_p", cur, refs, lam, result, mvp, preds, out)
 
     def leaf_predictors(self, part: dict, mvp: dict, out: torch.Tensor | None = None) -> torch.Tensor:
         """vame_mvp_gather on the leaves of a partition() or partition_bi()
@@ -879,10 +814,7 @@ class Engine:
         cus = part["cus"]
         if cus.dim() == 2 and cus.shape[1] == 12:
             self._check_cus(cus, 12)
-            wide = torch.zeros((cus.shape[0], 20), dtype=torch.int32, device=self.device)
-            wide[:, :12] = cus
-            wide[:, 12] = -1
-            cus = wide
+            cus = self._widen(cus)[0]
         self._check_cus(cus, 20)
         n = cus.shape[0]
         self._check_scalar(part["ncus"], "ncus")
@@ -902,11 +834,10 @@ class Engine:
         """modes: 1 = 2-CP only, 3 = 2-CP then 3-CP, plus MODE_FULL / MODE_HALF to
         code one alignment only.  Returns {(refIdx, MODE): (cost, cpmv)}."""
         cur = self._frame(cur)
-        refs = [self._frame(r) for r in refs]
+        refs, ref_ptrs = self._refs(refs, "affine_me_poc")
         out = out if out is not None else self.alloc_poc(len(refs), modes)
         self._check_poc_out(out, len(refs), modes)
         pr = _poc_result(out)
-        ref_ptrs = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
         check(lib().vame_affine_me_poc(self._h, _ptr(cur), ref_ptrs, len(refs), float(lam), modes,
                                        extra, ctypes.byref(pr), self._stream()))
         return out

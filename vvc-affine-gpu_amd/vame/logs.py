@@ -9,9 +9,8 @@ import os
 
 import numpy as np
 
-from ._lib import VameError, lib
-
-PREDS = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")  # constants.h:15-21 PRED_TYPES
+from ._lib import CUS_PER_CTU, VameError, lib
+from ._lib import MODES as PREDS  # constants.h:15-21 PRED_TYPES
 CPMVS_DTYPE = np.dtype([("nCPs", "<i4"), ("LTx", "<i4"), ("LTy", "<i4"), ("RTx", "<i4"),
                         ("RTy", "<i4"), ("LBx", "<i4"), ("LBy", "<i4")])
 
@@ -161,7 +160,7 @@ def _arrays(pred: int, width: int, height: int, cost: np.ndarray, cpmvs: np.ndar
     if cpmvs.dtype != CPMVS_DTYPE:
         cpmvs = np.ascontiguousarray(cpmvs, np.int32)
         assert cpmvs.ndim == 2 and cpmvs.shape[1] == 7
-    n = lib().vame_num_ctus(width, height) * (284 if pred >> 1 else 201)
+    n = lib().vame_num_ctus(width, height) * CUS_PER_CTU[pred >> 1]
     if cost.shape[0] != n or cpmvs.shape[0] != n:
         raise ValueError(f"results must hold {n} entries")
     return cost, cpmvs

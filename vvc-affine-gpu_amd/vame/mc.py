@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import lib
+from ._lib import CUS_PER_CTU, lib
 from .hostlogic import geometry
 
 CU_FIELDS = ("x", "y", "w", "h", "ref", "nCPs", "LTx", "LTy", "RTx", "RTy", "LBx", "LBy")
@@ -15,13 +15,13 @@ CTU = 128
 def candidate_geometry(W: int, H: int, align: int, groups=None):
     """(rows, x, y, w, h) int64 CPU tensors of the candidate CUs of an
     alignment in the frame, in the reference's index order
-    ctu * {201 | 284} + RETURN_STRIDE[group] + cuIdx (affine.cl:936 / :1929).
+    ctu * CUS_PER_CTU[align] + RETURN_STRIDE[group] + cuIdx (affine.cl:936 / :1929).
     groups: group indices into vame_group_geometry(align, .) and / or (w, h)
     sizes; None = every group."""
     n_ctus = lib().vame_num_ctus(W, H)
     if not n_ctus or align not in (0, 1):
         raise ValueError(f"unsupported resolution {W}x{H} or alignment {align}")
-    per = 284 if align else 201
+    per = CUS_PER_CTU[align]
     cols = (W + CTU - 1) // CTU  # integer ceil, as the engine's ctusPerRow
     geo = geometry(align)
     if groups is None:
@@ -53,14 +53,14 @@ def cus_from_result(W: int, H: int, align: int, ncp: int, cpmv: torch.Tensor, re
                     inframe_only: bool = True):
     """Descriptors [n, 12] int32 (columns CU_FIELDS, on cpmv's device) for the
     candidate CUs of `align` -- or of the size groups in `groups` -- with the
-    CPMVs of a result array `cpmv` ([nCtus * {201 | 284}, 7] as the engine
+    CPMVs of a result array `cpmv` ([nCtus * CUS_PER_CTU[align], 7] as the engine
     returns it, or its last 6 columns), and the int64 row indices kept.
     inframe_only drops the CUs that leave the frame (x + w > W or y + h > H),
     which the search prices at their rate alone and vame_affine_mc rejects."""
     if ncp not in (2, 3):
         raise ValueError("ncp must be 2 or 3")
     rows, x, y, w, h = candidate_geometry(W, H, align, groups)
-    n_all = lib().vame_num_ctus(W, H) * (284 if align else 201)
+    n_all = lib().vame_num_ctus(W, H) * CUS_PER_CTU[align]
     if cpmv.dim() != 2 or cpmv.shape[0] != n_all or cpmv.shape[1] not in (6, 7):
         raise ValueError(f"cpmv must be [{n_all}, 7] (or its last 6 columns)")
     if inframe_only:

@@ -13,10 +13,9 @@ import functools
 import numpy as np
 import torch
 
+from ._lib import CUS_PER_CTU as PER
 from ._lib import lib
 from .hostlogic import geometry
-
-PER = (201, 284)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,6 @@
-"""ctypes plumbing of vame_partition (include/vame.h): the CU partition
-decision on the search's result arrays, its outputs as device tensors, and
-to_host, which cuts them at the leaf count."""
+"""The outputs of vame_partition and vame_partition_bi (include/vame.h) as
+device tensors, to_host, which cuts them at the leaf count, and the candidate
+table.  Engine.partition / partition_bi make the calls."""
 from __future__ import annotations
 
 import ctypes
@@ -8,11 +8,9 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import PocResult, check, lib
+from ._lib import MAX_PENALTY, MODES, check, lib  # noqa: F401  (MAX_PENALTY: re-exported)
 
-MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
 KEYS = ("cus", "rows", "ncus", "ctu_info", "ctu_cost", "block_cu")
-MAX_PENALTY = 1 << 40
 
 
 def table() -> np.ndarray:
@@ -31,35 +29,27 @@ def result_preds(result: dict) -> int:
     return mask
 
 
+def alloc_keys(keys, cols: int, n_ctus: int, device) -> dict:
+    """The outputs `keys` of vame_partition (cols = 12) / vame_partition_bi (20)."""
+    shapes = {"cus": (n_ctus * 64, cols), "ncus": (), "ctu_info": (n_ctus, 4), "ctu_cost": (n_ctus,)}
+    return {k: torch.empty(shapes.get(k, (n_ctus * 64,)), dtype=torch.int64 if k == "ctu_cost" else torch.int32,
+                           device=device) for k in keys}
+
+
+def keys_to_host(keys, part: dict) -> dict:
+    """The outputs `keys` as numpy arrays, the per-leaf ones cut at the leaf
+    count (synchronizes: reads the count)."""
+    n = int(part["ncus"])
+    out = {k: part[k].cpu().numpy()[:n] if k in ("cus", "rows", "sel") else part[k].cpu().numpy() for k in keys}
+    out["ncus"] = n
+    return out
+
+
 def alloc(n_ctus: int, device) -> dict:
-    i32 = dict(dtype=torch.int32, device=device)
-    return {"cus": torch.empty((n_ctus * 64, 12), **i32), "rows": torch.empty(n_ctus * 64, **i32),
-            "ncus": torch.empty((), **i32), "ctu_info": torch.empty((n_ctus, 4), **i32),
-            "ctu_cost": torch.empty(n_ctus, dtype=torch.int64, device=device),
-            "block_cu": torch.empty(n_ctus * 64, **i32)}
-
-
-def partition(handle, n_ctus: int, device, result: dict, preds: int, split_penalty: int, stream, out=None) -> dict:
-    """One vame_partition call on `stream`; `result` is an alloc_poc dict
-    {(refIdx, MODE): (cost, cpmv)} that holds every PRED of `preds` for
-    refIdx 0 .. nrefs-1."""
-    nrefs = max(r for r, _ in result) + 1
-    pr = PocResult()
-    for (r, name), (cost, cpmv) in result.items():
-        m = MODES.index(name)
-        pr.cost[r][m] = cost.data_ptr()
-        pr.cpmvs[r][m] = cpmv.data_ptr()
-    part = out if out is not None else alloc(n_ctus, device)
-    V = ctypes.c_void_p
-    check(lib().vame_partition(handle, ctypes.byref(pr), nrefs, int(preds), int(split_penalty),
-                               *(V(part[k].data_ptr()) for k in KEYS), stream))
-    return part
+    return alloc_keys(KEYS, 12, n_ctus, device)
 
 
 def to_host(part: dict) -> dict:
     """The outputs as numpy arrays, cus and rows cut at the leaf count
     (synchronizes: reads the count)."""
-    n = int(part["ncus"])
-    out = {k: part[k].cpu().numpy() for k in KEYS}
-    out["cus"], out["rows"], out["ncus"] = out["cus"][:n], out["rows"][:n], n
-    return out
+    return keys_to_host(KEYS, part)

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import lib
+from ._lib import CUS_PER_CTU, lib
 from .mc import candidate_geometry
 
 
@@ -13,10 +13,10 @@ def cus_from_seeds(W: int, H: int, align: int, mv: torch.Tensor, ref: int = 0, s
     """2-CP descriptors [n, 12] int32 (vame.mc.CU_FIELDS, on mv's device), LT =
     RT = the row's seed and LB = 0, for the candidate CUs of `align` that lie
     wholly in the frame, and the int64 row indices kept.  mv: [nCtus *
-    {201 | 284}, 2] in 1/16 pel, as Engine.seed_search returns it.  skip_zero
+    CUS_PER_CTU[align], 2] in 1/16 pel, as Engine.seed_search returns it.  skip_zero
     drops the rows whose seed is (0, 0) -- the search's own start, which
     vame_affine_me_seeded skips."""
-    n_all = lib().vame_num_ctus(W, H) * (284 if align else 201)
+    n_all = lib().vame_num_ctus(W, H) * CUS_PER_CTU[bool(align)]
     if mv.dim() != 2 or tuple(mv.shape) != (n_all, 2):
         raise ValueError(f"mv must be [{n_all}, 2]")
     rows, x, y, w, h = candidate_geometry(W, H, align)

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import torch
 
-MODES = ("FULL_2CP", "FULL_3CP", "HALF_2CP", "HALF_3CP")
+from ._lib import MODES
 
 
 def pairs_per_poc(poc: int) -> int:

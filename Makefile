@@ -93,9 +93,13 @@ tests/native/anyorder_probe: tests/native/anyorder_probe.hip
 $(LIBDIR)/libvame.so: $(LIB_SRCS) $(LIB_HDRS)
 	$(call build_lib,$@,)
 
-$(BINDIR)/vame: $(PKG)/host/vame_main.cpp include/vame.h $(LIBDIR)/libvame.so
+# cli_options / cli_plan are host-only (no HIP include; tests/native/cli_check.cpp
+# builds them with g++), cli_worker and vame_main call HIP
+CLI_SRCS := $(addprefix $(PKG)/host/,vame_main.cpp cli_worker.cpp cli_options.cpp cli_plan.cpp)
+CLI_HDRS := $(wildcard $(PKG)/host/*.h) include/vame.h
+$(BINDIR)/vame: $(CLI_SRCS) $(CLI_HDRS) $(LIBDIR)/libvame.so
 	@mkdir -p $(BINDIR)
-	$(HIPCC) -O2 -std=c++17 -Wall -o $@ $(PKG)/host/vame_main.cpp \
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ $(CLI_SRCS) \
 	    -L$(LIBDIR) -lvame -Wl,-rpath,'$$ORIGIN/../lib' -lpthread
 
 oracle:

@@ -174,6 +174,37 @@ def test_cli_2cp_only_and_extra_iters(tmp_path):
         assert (tmp_path / ("raw_" + f)).read_bytes() == (exp / f).read_bytes()
 
 
+def test_cli_issue_loop_edges(seq416):
+    """The ends of the worker's issue loop, each against the oracle's logs.
+    -f 1 --devices 0,0: one POC, one batch, the second worker never started.
+    -f 3 --per-launch --align half --modes 2cp: one PRED of four coded, so the
+    per-launch timing events [r * 4 + m] are used at m = 2 alone, and the
+    third batch reuses the first one's result slot."""
+    tmp, orig, recon, exp = seq416
+    one = tmp / "expected_f1"
+    one.mkdir()
+    expected_logs(one, orig[:1], recon[:1], 32)
+    out, stdout = run_cli(tmp, 416, 240, 1, 32, ["--devices", "0,0"], name="one_poc_two_workers")
+    assert len(compare_dirs(out, one)) == 40
+    assert stdout.count("COMPUTING ON GPU 0") == 2 and "TOTAL_EXEC_TIME(1x)," in stdout
+
+    half = tmp / "expected_half_2cp"
+    half.mkdir()
+    expected_logs(half, orig[:3], recon[:3], 32, modes=(2,))
+    out, stdout = run_cli(tmp, 416, 240, 3, 32, ["--per-launch", "--align", "half", "--modes", "2cp"],
+                          name="per_launch_half_2cp")
+    files = sorted(os.listdir(out))
+    assert files and all("_HALF_2CPs_" in f for f in files), files
+    assert files == sorted(f for f in os.listdir(half) if "HALF" in f)
+    for f in files:
+        assert (out / f).read_bytes() == (half / f).read_bytes(), f
+    t = {l.split(",")[0]: float(l.split(",")[1]) for l in stdout.splitlines()
+         if l.endswith(tuple("0123456789")) and "_EXEC," in l}
+    assert t["FULL_2CP_EXEC"] == 0 and t["FULL_3CP_EXEC"] == 0 and t["HALF_3CP_EXEC"] == 0
+    assert t["HALF_2CP_EXEC"] > 0
+    assert "PRED_EXEC_SOURCE,measured" in stdout.splitlines()
+
+
 def test_cli_1080p_c1(tmp_path):
     """BASELINE configs[0] shape: 1920x1080 QP32, 2 frames, all modes."""
     orig, recon = synth_sequence(1920, 1080, 2, qp=32)

@@ -110,6 +110,36 @@ def test_templates_check_passes_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "templates_check ok" in r.stdout, (r.stdout + r.stderr)[-2000:]
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_cli_check_passes_under_sanitizers(tmp_path):
+    """tests/native/cli_check.cpp, built with the CLI's host-only units
+    (cli_options.cpp, cli_plan.cpp) and the library's host-only ones as a plain
+    C++ program under ASan + UBSan (their runtimes linked into the program):
+    the option parser and the Settings, the dealing of POCs to workers, the
+    batches, the recon labels, the result layout and the apportioning.  The
+    pred_work values it prints (FULL_2CP, FULL_3CP, HALF_2CP, HALF_3CP) are the
+    sub-block predictions pair_accounting counts on its own, per CP count over
+    both alignments."""
+    import subprocess
+    exe = str(tmp_path / "cli_check")
+    host, csrc = (os.path.join(REPO, "vvc-affine-gpu_amd", d) for d in ("host", "csrc"))
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-o", exe,
+                        os.path.join(REPO, "tests", "native", "cli_check.cpp"),
+                        os.path.join(host, "cli_options.cpp"), os.path.join(host, "cli_plan.cpp"),
+                        os.path.join(csrc, "vame_hostlogic.cpp"), os.path.join(csrc, "vame_templates.cpp")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "cli_check ok" in r.stdout, (r.stdout + r.stderr)[-2000:]
+    rows = re.findall(r"^pred_work (\d+)x(\d+) extra (\d+): (\d+) (\d+) (\d+) (\d+)$", r.stdout, flags=re.M)
+    assert sorted((int(W), int(H), int(e)) for W, H, e, *_ in rows) == [
+        (416, 240, 0), (416, 240, 2), (1920, 1080, 0), (1920, 1080, 2)]
+    for W, H, extra, f2, f3, h2, h3 in (map(int, row) for row in rows):
+        assert f2 + h2 == pair_accounting(W, H, (2,), extra)["sb_pred"], (W, H, extra)
+        assert f3 + h3 == pair_accounting(W, H, (3,), extra)["sb_pred"], (W, H, extra)
+
+
 def test_engine_reads_at_most_five_knobs():
     """the product library reads at most five environment
     variables, each documented in include/vame.h; over every source file of

@@ -37,225 +37,53 @@
 //  * extra keys after the reference's: FUSED_POC_EXEC, PRED_EXEC_SOURCE,
 //    READ_CSV_TIME (ingest), LOG_WRITE_TIME (host time formatting + writing
 //    the logs, overlapped with the GPU), LOG_BYTES.
+//
+// The units: cli_options (command line -> Settings), cli_plan (layout, POC
+// dealing, batches, apportioning; both host-only), cli_worker (one device's
+// work), and this file, the sequence that joins them.
 #include <hip/hip_runtime.h>
 #include <sys/time.h>
 #include <time.h>
 
-#include <algorithm>
-#include <condition_variable>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <set>
-#include <sstream>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/vame.h"
+#include "cli_worker.h"
+
+using namespace vame_cli;
 
 namespace {
-
-// ------------------------------------------------------------ options
-struct Opt {
-  const char* name;
-  char shortc;
-  bool has_default;
-  std::string def;
-  const char* help;
-  bool set = false;
-  std::string val;
-};
-
-struct Cli {
-  std::vector<Opt> opts;
-  std::vector<std::string> flags_set;  // value-less extension flags
-  int find(const std::string& n) {
-    for (size_t i = 0; i < opts.size(); i++)
-      if (n == opts[i].name) return (int)i;
-    // boost's allow_guessing: a unique prefix of a long option name
-    int hit = -1;
-    for (size_t i = 0; i < opts.size(); i++)
-      if (strncmp(opts[i].name, n.c_str(), n.size()) == 0) {
-        if (hit >= 0) return -2;
-        hit = (int)i;
-      }
-    return hit;
-  }
-  int find_short(char c) {
-    for (size_t i = 0; i < opts.size(); i++)
-      if (opts[i].shortc == c) return (int)i;
-    return -1;
-  }
-  bool has(const char* n) { return opts[find(n)].set; }
-  std::string str(const char* n) {
-    Opt& o = opts[find(n)];
-    return o.set ? o.val : o.def;
-  }
-  int num(const char* n) { return atoi(str(n).c_str()); }
-  bool defaulted(const char* n) { return !opts[find(n)].set; }
-};
-
-void print_help(Cli& c) {
-  printf("Allowed options:\n");
-  printf("  -h [ --help ]                         produce help message\n");
-  for (auto& o : c.opts) {
-    char lhs[96];
-    if (o.shortc)
-      snprintf(lhs, sizeof lhs, "  -%c [ --%s ] arg%s", o.shortc, o.name,
-               o.has_default ? (" (=" + o.def + ")").c_str() : "");
-    else
-      snprintf(lhs, sizeof lhs, "  --%s arg%s", o.name,
-               o.has_default ? (" (=" + o.def + ")").c_str() : "");
-    printf("%-40s%s\n", lhs, o.help);
-  }
-  printf("%-40s%s\n", "  --per-launch",
-         "one launch per (refIdx, PRED) like the reference (per-PRED kernel times)");
-  printf("%-40s%s\n", "  --prof",
-         "PROF on (the reference's enablePROF, hard-coded 0 there)");
-}
-
-// Returns 0 ok, 1 help, 2 error.
-int parse(Cli& c, int argc, char** argv) {
-  for (int i = 1; i < argc; i++) {
-    std::string a = argv[i];
-    int idx = -1;
-    std::string val;
-    bool have_val = false;
-    if (a.size() > 2 && a[0] == '-' && a[1] == '-') {
-      std::string n = a.substr(2);
-      size_t eq = n.find('=');
-      if (eq != std::string::npos) {
-        val = n.substr(eq + 1);
-        n = n.substr(0, eq);
-        have_val = true;
-      }
-      if (n == "help") return 1;
-      if (n == "per-launch" || n == "prof") {
-        c.flags_set.push_back(n);
-        continue;
-      }
-      idx = c.find(n);
-      if (idx == -2) {
-        fprintf(stderr, "option '--%s' is ambiguous\n", n.c_str());
-        return 2;
-      }
-    } else if (a.size() >= 2 && a[0] == '-') {
-      if (a[1] == 'h' && a.size() == 2) return 1;
-      idx = c.find_short(a[1]);
-      if (a.size() > 2) {
-        val = a.substr(2);
-        have_val = true;
-      }
-    } else {
-      fprintf(stderr, "unexpected positional argument '%s'\n", a.c_str());
-      return 2;
-    }
-    if (idx < 0) {
-      fprintf(stderr, "unrecognised option '%s'\n", a.c_str());
-      return 2;
-    }
-    if (!have_val) {
-      if (i + 1 >= argc) {
-        fprintf(stderr, "the required argument for option '--%s' is missing\n", c.opts[idx].name);
-        return 2;
-      }
-      val = argv[++i];
-    }
-    c.opts[idx].set = true;
-    c.opts[idx].val = val;
-  }
-  return 0;
-}
-
-// main_aux_functions.h:77-145 checkReportParameters
-int check_report(Cli& c) {
-  int errors = 0;
-  printf("-=-= INPUT PARAMETERS =-=-\n");
-  if (c.defaulted("DeviceIndex"))
-    printf("  Device index not set. Using standard value of %d.\n", c.num("DeviceIndex"));
-  else
-    printf("  Device Index=%d\n", c.num("DeviceIndex"));
-  if (c.defaulted("CpmvLogFile"))
-    printf("  CPMVs log file not set. The output will not be written to any file.\n");
-  else
-    printf("  CpmvLogFile=%s\n", c.str("CpmvLogFile").c_str());
-  if (c.has("QP"))
-    printf("  QP=%d\n", c.num("QP"));
-  else {
-    printf("  [!] ERROR: QP not set.\n");
-    errors++;
-  }
-  if (c.has("FramesToBeEncoded"))
-    printf("  FramesToBeEncoded=%d\n", c.num("FramesToBeEncoded"));
-  else {
-    printf("  [!] ERROR: FramesToBeEncoded not set.\n");
-    errors++;
-  }
-  if (c.defaulted("ExtraGradientIter"))
-    printf("  ExtraGradientIter not specified. Using zero extra gradients (i.e., 5 iterations for 2 "
-           "CPs and 4 iterations for 3 CPs).\n");
-  else {
-    const int e = c.num("ExtraGradientIter");
-    printf("  ExtraGradientIter=%d. Using a total of %d iterations for 2 CPs and %d iterations for "
-           "3 CPs.\n",
-           e, 5 + e, 4 + e);
-  }
-  if (c.has("Resolution"))
-    printf("  Resolution=%s\n", c.str("Resolution").c_str());
-  else {
-    printf("  [!] ERROR: Resolution not set.\n");
-    errors++;
-  }
-  if (c.has("OriginalFrames"))
-    printf("  InputOriginalFrame=%s\n", c.str("OriginalFrames").c_str());
-  else {
-    printf("  [!] ERROR: Input original frames not set.\n");
-    errors++;
-  }
-  if (c.has("ReferenceFrames"))
-    printf("  InputReferenceFrame=%s\n", c.str("ReferenceFrames").c_str());
-  else {
-    printf("  [!] ERROR: Input reference frames not set.\n");
-    errors++;
-  }
-  return errors;
-}
-
-// main_aux_functions.h:59-68
-// Algorithmic work of one PRED of one (POC, ref) pair: sub-block predictions
-// over the in-frame CUs (affine.cl:192-193; n_pred 6 / 5 for 2 / 3 CP, + extra
-// iterations, affine.cl:172-177) -- the weights that apportion a fused
-// launch's kernel time to the reference's per-PRED keys.
-double pred_work(int W, int H, int align, int ncp, int extra) {
-  const int cols = (W + 127) / 128, rows = (H + 127) / 128;
-  double sb = 0;
-  int w, h, n, stride, xs[64], ys[64];
-  for (int g = 0; g < vame_num_groups(align); g++) {
-    if (vame_group_geometry(align, g, &w, &h, &n, &stride, xs, ys)) continue;
-    for (int ctu = 0; ctu < cols * rows; ctu++)
-      for (int k = 0; k < n; k++) {
-        const int x = (ctu % cols) * 128 + xs[k], y = (ctu / cols) * 128 + ys[k];
-        if (x + w <= W && y + h <= H) sb += (double)(w / 4) * (h / 4);
-      }
-  }
-  return sb * ((ncp == 2 ? 6 : 5) + extra);
-}
 
 void print_timestamp(const char* msg) {
   struct timeval tv;
   gettimeofday(&tv, nullptr);
   struct tm* t = localtime(&tv.tv_sec);
-  printf("%s @ %02d:%02d:%02d.%03d\n", msg, t->tm_hour, t->tm_min, t->tm_sec,
-         (int)(tv.tv_usec / 1000));
+  printf("%s @ %02d:%02d:%02d.%03d\n", msg, t->tm_hour, t->tm_min, t->tm_sec, (int)(tv.tv_usec / 1000));
 }
 
-double now_s() {
-  struct timeval tv;
-  gettimeofday(&tv, nullptr);
-  return (double)tv.tv_sec + (double)tv.tv_usec / 1e6;
+// The OpenCL listing of main.cpp:133-247, as HIP, and the check of the chosen
+// devices.  False (after the reference's message) if one does not exist.
+bool list_devices(const std::vector<int>& devices) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
+  for (int d = 0; d < ndev; d++) {
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, d) != hipSuccess) continue;
+    printf("GPU %d\n\t%s (%s)\n", d, p.name, p.gcnArchName);
+  }
+  for (int d : devices)
+    if (d < 0 || d >= ndev) {
+      printf("Incorrect GPU index. Only %d GPUs are detected\n", ndev);
+      return false;
+    }
+  for (int d : devices) {
+    hipDeviceProp_t p;
+    (void)hipGetDeviceProperties(&p, d);
+    printf("COMPUTING ON GPU %d\n", d);
+    printf("-- Max compute units %d\n", p.multiProcessorCount);
+  }
+  return true;
 }
 
 // main_aux_functions.h:1499-1545 testReferences (prints POC 1 .. N-1)
@@ -265,601 +93,104 @@ void test_references(int n_frames, int qp) {
   for (int f = 1; f < n_frames; f++) {
     int refs[4];
     const int n = vame_ref_list(f, refs);
-    printf("POC %3d   QP %d motionLambda %f : [L0 %d", f, vame_poc_qp(qp, f),
-           (double)vame_lambda(qp, f), refs[0]);
+    printf("POC %3d   QP %d motionLambda %f : [L0 %d", f, vame_poc_qp(qp, f), (double)vame_lambda(qp, f), refs[0]);
     for (int r = 1; r < n; r++) printf(" %d", refs[r]);
     printf("]\n");
   }
 }
 
-// ------------------------------------------------------------ results
-constexpr int kFull = 201, kHalf = 284;
-constexpr int kBatchPocs = 4;  // POCs per vame_affine_me_batch call (<= 16 pairs)
-
-struct Layout {  // one POC's results: [ref][pred] cost block, then cpmvs block
-  size_t off_cost[4][4], off_cp[4][4], bytes;
-  Layout(int nCtus) {
-    size_t o = 0;
-    for (int r = 0; r < 4; r++)
-      for (int m = 0; m < 4; m++) {
-        const size_t n = (size_t)nCtus * ((m >> 1) ? kHalf : kFull);
-        off_cost[r][m] = o;
-        o += n * sizeof(int64_t);
-        off_cp[r][m] = o;
-        o += (n * sizeof(vame_cpmvs) + 255) & ~size_t(255);
-      }
-    bytes = o;
+// The sample files into orig / recon (main.cpp:308-330); the seconds it took
+// in *read_s.  False after its message.
+bool ingest(const Settings& s, std::vector<uint16_t>& orig, std::vector<uint16_t>& recon, double* t_read0,
+            double* read_s) {
+  const size_t fsz = (size_t)s.W * s.H;
+  orig.resize(fsz * s.frames);
+  recon.resize(fsz * s.frames);
+  FILE* a = fopen(s.orig_path.c_str(), "r");
+  FILE* b = fopen(s.recon_path.c_str(), "r");
+  if (!a || !b) {
+    perror("error while opening samples files");
+    return false;
   }
-};
-
-struct Slab {
-  char* host = nullptr;  // pinned
-  int owner = 0;         // the worker whose pool it returns to
-  int poc = 0, nrefs = 0;
-  float pred_ns[4] = {0, 0, 0, 0};  // per-launch mode kernel times
-  float fused_ns = 0;
-};
-
-struct Shared {
-  std::mutex mu;
-  std::condition_variable cv;
-  // one pool per worker: a worker running ahead of the in-order writer can only
-  // exhaust its own slabs, never the ones the writer is waiting for
-  std::vector<std::vector<Slab*>> pools;
-  std::map<int, Slab*> done;
-  std::string error;
-  bool failed = false;
-};
-
-struct Job {
-  int worker, device, W, H, nCtus, qp, extra, mode_mask;
-  bool per_launch;
-  bool prof;
-  std::vector<int> pocs;
-  const uint16_t* orig;   // host, POC p at frame p-1
-  const uint16_t* recon;  // host, POC p at frame p
-  const Layout* L;
-  Shared* S;
-};
-
-#define GPU_CHECK(x, what)                                                               \
-  do {                                                                                   \
-    hipError_t e_ = (x);                                                                 \
-    if (e_ != hipSuccess) {                                                              \
-      fail(S, std::string(what) + ": " + hipGetErrorString(e_));                         \
-      return;                                                                            \
-    }                                                                                    \
-  } while (0)
-#define VAME_CHECK(x, what)                                                              \
-  do {                                                                                   \
-    int rc_ = (x);                                                                       \
-    if (rc_ != 0) {                                                                      \
-      fail(S, std::string(what) + ": " + vame_strerror(rc_) + " " + vame_last_hip_error()); \
-      return;                                                                            \
-    }                                                                                    \
-  } while (0)
-
-void fail(Shared* S, const std::string& msg) {
-  std::lock_guard<std::mutex> g(S->mu);
-  if (!S->failed) S->error = msg;
-  S->failed = true;
-  S->cv.notify_all();
-}
-
-// One device: runs its POCs in order on one stream, uploading each batch's
-// frames on a second stream while the previous batch computes, and hands each
-// POC's results (pinned host slab) to the writer.
-void gpu_worker(Job J) {
-  Shared* S = J.S;
-  // VAME_CLI_TRACE=1: the worker's timeline on stderr (host and GPU)
-  const bool trace = getenv("VAME_CLI_TRACE") && atoi(getenv("VAME_CLI_TRACE")) != 0;
-  const double w0 = now_s();
-  GPU_CHECK(hipSetDevice(J.device), "hipSetDevice");
-  vame_ctx* ctx = nullptr;
-  VAME_CHECK(vame_create(&ctx, J.device, J.W, J.H), "vame_create");
-  // a batch holds at most kBatchPocs POCs of <= 4 pairs: the seed-reuse
-  // scratch for that many pairs per launch (half of the default)
-  VAME_CHECK(vame_set_max_pairs(ctx, 4 * kBatchPocs), "vame_set_max_pairs");
-  const double w1 = now_s();
-  VAME_CHECK(vame_set_prof(ctx, J.prof ? 1 : 0), "vame_set_prof");
-  hipStream_t st, up, dn;  // compute; frame uploads; result downloads
-  GPU_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-  // The copy streams are created with an explicit priority: created like the
-  // compute stream, one of them shared its hardware queue with it (HIP maps
-  // streams onto GPU_MAX_HW_QUEUES = 4 queues, and this process has five
-  // streams), so each batch's 285 MB result download at C5 (5.1 ms at PCIe
-  // rate) sat in front of the next batch's kernels: 0.30 s of idle GPU per
-  // 240 4K frames (VAME_CLI_TRACE).  VAME_CLI_COPY_PRIO=0 restores that.
-  const int copyPrio = getenv("VAME_CLI_COPY_PRIO") ? atoi(getenv("VAME_CLI_COPY_PRIO")) : 1;
-  if (copyPrio) {
-    int lo = 0, hi = 0;
-    GPU_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange");
-    const int pr = copyPrio > 0 ? lo : hi;
-    GPU_CHECK(hipStreamCreateWithPriority(&up, hipStreamNonBlocking, pr), "hipStreamCreate");
-    GPU_CHECK(hipStreamCreateWithPriority(&dn, hipStreamNonBlocking, pr), "hipStreamCreate");
-  } else {
-    GPU_CHECK(hipStreamCreateWithFlags(&up, hipStreamNonBlocking), "hipStreamCreate");
-    GPU_CHECK(hipStreamCreateWithFlags(&dn, hipStreamNonBlocking), "hipStreamCreate");
-  }
-  const size_t fsz = (size_t)J.W * J.H;
-  // frames: orig of each POC, recon of every label its ring holds -- allocated
-  // here in two blocks, uploaded per batch (upload_frames below)
-  std::map<int, uint16_t*> dorig, drecon;
-  uint16_t *origBlk = nullptr, *reconBlk = nullptr;
-  {
-    std::vector<int> labels;
-    for (int p : J.pocs) {
-      int refs[4];
-      const int n = vame_ref_list(p, refs);
-      for (int r = 0; r < n; r++)
-        if (std::find(labels.begin(), labels.end(), refs[r]) == labels.end()) labels.push_back(refs[r]);
-    }
-    GPU_CHECK(hipMalloc(&origBlk, J.pocs.size() * fsz * 2), "hipMalloc frames");
-    GPU_CHECK(hipMalloc(&reconBlk, labels.size() * fsz * 2), "hipMalloc frames");
-    for (size_t i = 0; i < J.pocs.size(); i++) dorig[J.pocs[i]] = origBlk + i * fsz;
-    for (size_t i = 0; i < labels.size(); i++) drecon[labels[i]] = reconBlk + i * fsz;
-  }
-  // POCs run in batches: the fused path hands a batch of up to kBatchPocs POCs
-  // (<= 32 (POC, refIdx) pairs) to one vame_affine_me_batch call, so they share
-  // launches; --per-launch keeps the reference's one launch per (refIdx, PRED)
-  const int B = J.per_launch ? 1 : kBatchPocs;
-  std::vector<std::vector<int>> batches;
-  for (size_t i = 0, pairs = 0; i < J.pocs.size(); i++) {
-    const int n = std::min(4, J.pocs[i]);
-    if (batches.empty() || (int)batches.back().size() == B || pairs + n > 32) {
-      batches.push_back({});
-      pairs = 0;
-    }
-    batches.back().push_back(J.pocs[i]);
-    pairs += n;
-  }
-  // Frames go up on their own stream from a thread of their own, batch by
-  // batch ahead of the kernels (copies from pageable host memory block the
-  // calling thread, so the launching thread never waits for them); batch b's
-  // kernels wait for upEv[b] on the device.
-  std::vector<hipEvent_t> upEv(batches.size());
-  for (auto& e : upEv) GPU_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-  std::mutex upMu;
-  std::condition_variable upCv;
-  size_t upDone = 0;      // batches whose uploads are issued and whose event is recorded
-  bool upFailed = false;
-  struct Joiner {
-    std::thread t;
-    ~Joiner() {
-      if (t.joinable()) t.join();
-    }
-  } uploader;
-  uploader.t = std::thread([&] {
-    hipError_t e = hipSetDevice(J.device);
-    std::set<const uint16_t*> uploaded;
-    auto put = [&](uint16_t* dst, const uint16_t* src) {
-      if (e == hipSuccess && uploaded.insert(dst).second)
-        e = hipMemcpyAsync(dst, src, fsz * 2, hipMemcpyHostToDevice, up);
-    };
-    for (size_t b = 0; b < batches.size() && e == hipSuccess; b++) {
-      {
-        std::lock_guard<std::mutex> g(S->mu);
-        if (S->failed) break;
-      }
-      for (int p : batches[b]) {
-        put(dorig[p], J.orig + (size_t)(p - 1) * fsz);
-        int refs[4];
-        const int n = vame_ref_list(p, refs);
-        for (int r = 0; r < n; r++) put(drecon[refs[r]], J.recon + (size_t)refs[r] * fsz);
-      }
-      if (e == hipSuccess) e = hipEventRecord(upEv[b], up);
-      std::lock_guard<std::mutex> g(upMu);
-      if (e == hipSuccess) upDone = b + 1;
-      upCv.notify_all();
-    }
-    std::lock_guard<std::mutex> g(upMu);
-    upFailed = e != hipSuccess || upDone < batches.size();
-    upCv.notify_all();
-  });
-  char* dres = nullptr;  // two batch slots of B POC layouts each
-  GPU_CHECK(hipMalloc(&dres, 2 * (size_t)B * J.L->bytes), "hipMalloc results");
-  // two slots: batch k+1 is enqueued before the host waits for batch k's
-  // copies, which run on their own stream while batch k+1 computes (batch
-  // k+2 reuses the slot only after the host saw those copies complete)
-  hipEvent_t e0[2], e1[2], computed[2], copied[2];
-  for (int i = 0; i < 2; i++) {
-    GPU_CHECK(hipEventCreate(&e0[i]), "hipEventCreate");
-    GPU_CHECK(hipEventCreate(&e1[i]), "hipEventCreate");
-    GPU_CHECK(hipEventCreateWithFlags(&computed[i], hipEventDisableTiming), "hipEventCreate");
-    GPU_CHECK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming), "hipEventCreate");
-  }
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs[2];  // per-launch timing events
-  std::vector<Slab*> pending;
-  int pslot = 0;
-  hipEvent_t tStart, tFirst, tLast;  // trace: stream start, first and last kernel boundary
-  GPU_CHECK(hipEventCreate(&tStart), "hipEventCreate");
-  GPU_CHECK(hipEventCreate(&tFirst), "hipEventCreate");
-  GPU_CHECK(hipEventCreate(&tLast), "hipEventCreate");
-  GPU_CHECK(hipEventRecord(tStart, st), "hipEventRecord");
-  const double w2 = now_s();
-  double wFirst = 0, kernelSum = 0;
-  int late = 0;  // trace: batches issued after the previous one had finished on the GPU
-  std::vector<hipEvent_t> gs(batches.size()), ge(batches.size());  // trace: per-batch GPU boundaries
-
-  // waits for a slot's copies, collects its kernel times, hands the slabs to the writer
-  auto finish = [&](std::vector<Slab*>& batch, int slot) -> bool {
-    if (hipEventSynchronize(copied[slot]) != hipSuccess) return false;
-    float ms = 0;
-    if (J.per_launch) {
-      Slab* s = batch[0];
-      for (int r = 0; r < s->nrefs; r++)
-        for (int m = 0; m < 4; m++) {
-          if (!((vame_pred_mask(J.mode_mask) >> m) & 1)) continue;
-          if (hipEventElapsedTime(&ms, evs[slot][r * 4 + m].first, evs[slot][r * 4 + m].second))
-            return false;
-          s->pred_ns[m] += ms * 1e6f;
-        }
-    } else {
-      if (hipEventElapsedTime(&ms, e0[slot], e1[slot]) != hipSuccess) return false;
-      batch[0]->fused_ns = ms * 1e6f;  // the batch's kernel time, reported once
-      kernelSum += ms;
-    }
-    std::lock_guard<std::mutex> g(S->mu);
-    for (Slab* s : batch) S->done[s->poc] = s;
-    S->cv.notify_all();
-    return true;
-  };
-
-  for (size_t k = 0; k < batches.size(); k++) {
-    const int slot = (int)(k & 1);
-    std::vector<Slab*> batch;
-    for (int p : batches[k]) {
-      const int n = std::min(4, p);
-      Slab* slab = nullptr;
-      {
-        std::unique_lock<std::mutex> g(S->mu);
-        auto& pool = S->pools[J.worker];
-        S->cv.wait(g, [&] { return S->failed || !pool.empty(); });
-        if (S->failed) return;
-        slab = pool.back();
-        pool.pop_back();
-      }
-      slab->poc = p;
-      slab->nrefs = n;
-      batch.push_back(slab);
-    }
-    {  // this batch's frames: issued by the uploader, then waited for on the device
-      std::unique_lock<std::mutex> g(upMu);
-      upCv.wait(g, [&] { return upDone > k || upFailed; });
-      if (upDone <= k) {
-        fail(S, "upload frames failed");
-        return;
-      }
-    }
-    GPU_CHECK(hipStreamWaitEvent(st, upEv[k], 0), "hipStreamWaitEvent");
-    if (trace && k > 0 && hipEventQuery(computed[slot ^ 1]) == hipSuccess) late++;  // the GPU waited for this thread
-    if (trace) {
-      GPU_CHECK(hipEventCreate(&gs[k]), "hipEventCreate");
-      GPU_CHECK(hipEventCreate(&ge[k]), "hipEventCreate");
-      GPU_CHECK(hipEventRecord(gs[k], st), "hipEventRecord");
-    }
-    if (k == 0) {
-      GPU_CHECK(hipEventRecord(tFirst, st), "hipEventRecord");
-      wFirst = now_s();
-    }
-    auto base = [&](int j) { return dres + ((size_t)slot * B + j) * J.L->bytes; };
-    if (J.per_launch) {
-      // main.cpp:754-966: per refIdx, FULL_2CP, FULL_3CP, HALF_2CP, HALF_3CP
-      const int p = batch[0]->poc;
-      int refs[4];
-      const int nrefs = vame_ref_list(p, refs);
-      const float lambda = vame_lambda(J.qp, p);
-      auto dcost = [&](int r, int m) { return (int64_t*)(base(0) + J.L->off_cost[r][m]); };
-      auto dcp = [&](int r, int m) { return (vame_cpmvs*)(base(0) + J.L->off_cp[r][m]); };
-      while (evs[slot].size() < (size_t)nrefs * 4) {
-        std::pair<hipEvent_t, hipEvent_t> e;
-        GPU_CHECK(hipEventCreate(&e.first), "hipEventCreate");
-        GPU_CHECK(hipEventCreate(&e.second), "hipEventCreate");
-        evs[slot].push_back(e);
-      }
-      for (int r = 0; r < nrefs; r++)
-        for (int m = 0; m < 4; m++) {
-          if (!((vame_pred_mask(J.mode_mask) >> m) & 1)) continue;
-          auto& e = evs[slot][r * 4 + m];
-          GPU_CHECK(hipEventRecord(e.first, st), "hipEventRecord");
-          VAME_CHECK(vame_affine_me(ctx, drecon[refs[r]], dorig[p], lambda, m >> 1, (m & 1) ? 3 : 2,
-                                    J.extra, (m & 1) ? dcp(r, m - 1) : nullptr, dcost(r, m),
-                                    dcp(r, m), st),
-                     "vame_affine_me");
-          GPU_CHECK(hipEventRecord(e.second, st), "hipEventRecord");
-        }
-    } else {
-      vame_poc_result out[kBatchPocs];
-      const uint16_t* rp[kBatchPocs][4];
-      vame_poc_job jobs[kBatchPocs];
-      for (size_t j = 0; j < batch.size(); j++) {
-        const int p = batch[j]->poc;
-        int refs[4];
-        const int nrefs = vame_ref_list(p, refs);
-        memset(&out[j], 0, sizeof out[j]);
-        for (int r = 0; r < nrefs; r++) {
-          rp[j][r] = drecon[refs[r]];
-          for (int m = 0; m < 4; m++) {
-            if (!((vame_pred_mask(J.mode_mask) >> m) & 1)) continue;
-            out[j].cost[r][m] = (int64_t*)(base((int)j) + J.L->off_cost[r][m]);
-            out[j].cpmvs[r][m] = (vame_cpmvs*)(base((int)j) + J.L->off_cp[r][m]);
-          }
-        }
-        jobs[j] = vame_poc_job{dorig[p], rp[j], nrefs, vame_lambda(J.qp, p), &out[j]};
-      }
-      GPU_CHECK(hipEventRecord(e0[slot], st), "hipEventRecord");
-      VAME_CHECK(vame_affine_me_batch(ctx, jobs, (int)batch.size(), J.mode_mask, J.extra, st),
-                 "vame_affine_me_batch");
-      GPU_CHECK(hipEventRecord(e1[slot], st), "hipEventRecord");
-    }
-    if (trace) GPU_CHECK(hipEventRecord(ge[k], st), "hipEventRecord");
-    GPU_CHECK(hipEventRecord(computed[slot], st), "hipEventRecord");
-    if (k + 1 == batches.size()) GPU_CHECK(hipEventRecord(tLast, st), "hipEventRecord");
-    GPU_CHECK(hipStreamWaitEvent(dn, computed[slot], 0), "hipStreamWaitEvent");
-    for (size_t j = 0; j < batch.size(); j++)
-      GPU_CHECK(hipMemcpyAsync(batch[j]->host, base((int)j), J.L->bytes, hipMemcpyDeviceToHost, dn),
-                "D2H");
-    GPU_CHECK(hipEventRecord(copied[slot], dn), "hipEventRecord");
-    if (!pending.empty() && !finish(pending, pslot)) {
-      fail(S, "waiting for results failed");
-      return;
-    }
-    pending = batch;
-    pslot = slot;
-  }
-  if (!pending.empty() && !finish(pending, pslot)) {
-    fail(S, "waiting for results failed");
-    return;
-  }
-  if (trace) {
-    float toFirst = 0, span = 0;
-    (void)hipEventElapsedTime(&toFirst, tStart, tFirst);
-    (void)hipEventElapsedTime(&span, tFirst, tLast);
-    fprintf(stderr,
-            "[trace] worker %d: host create %.1f ms, allocations %.1f ms, first launch issued at %.1f ms, "
-            "results in at %.1f ms; GPU: stream start -> first launch %.1f ms, first launch -> last "
-            "kernel %.1f ms, kernels %.1f ms (gaps %.1f ms)\n",
-            J.worker, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (wFirst - w0) * 1e3, (now_s() - w0) * 1e3, toFirst,
-            span, kernelSum, span - kernelSum);
-    fprintf(stderr, "[trace] worker %d: %d of %zu batches issued after the previous one had finished; gaps (ms):",
-            J.worker, late, batches.size());
-    for (size_t b = 1; b < batches.size(); b++) {
-      float g = 0, len = 0;
-      (void)hipEventElapsedTime(&g, ge[b - 1], gs[b]);
-      (void)hipEventElapsedTime(&len, gs[b], ge[b]);
-      fprintf(stderr, " %.2f/%.1f", g, len);
-    }
-    fprintf(stderr, "\n");
-    for (size_t b = 0; b < batches.size(); b++) {
-      (void)hipEventDestroy(gs[b]);
-      (void)hipEventDestroy(ge[b]);
-    }
-  }
-  (void)hipEventDestroy(tStart);
-  (void)hipEventDestroy(tFirst);
-  (void)hipEventDestroy(tLast);
-  for (int i = 0; i < 2; i++) {
-    for (auto& e : evs[i]) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    (void)hipEventDestroy(e0[i]);
-    (void)hipEventDestroy(e1[i]);
-    (void)hipEventDestroy(computed[i]);
-    (void)hipEventDestroy(copied[i]);
-  }
-  if (uploader.t.joinable()) uploader.t.join();
-  for (auto& e : upEv) (void)hipEventDestroy(e);
-  (void)hipFree(origBlk);
-  (void)hipFree(reconBlk);
-  (void)hipFree(dres);
-  (void)hipStreamDestroy(up);
-  (void)hipStreamDestroy(dn);
-  (void)hipStreamDestroy(st);
-  vame_destroy(ctx);
-}
-
-}  // namespace
-
-int main(int argc, char** argv) {
-  Cli c;
-  c.opts = {
-      {"DeviceIndex", 0, true, "0", "Index of the GPU device according ot clinfo command"},
-      {"QP", 'q', false, "", "Quantization parameter"},
-      {"FramesToBeEncoded", 'f', false, "", "Number of frames to be processed"},
-      {"ExtraGradientIter", 0, true, "0",
-       "Number of extra iterations during Gradient-based Affine ME"},
-      {"Resolution", 's', false, "", "Resolution of the video, in the format 1920x1080"},
-      {"OriginalFrames", 'o', false, "", "Input file for original frames samples"},
-      {"ReferenceFrames", 'r', false, "", "Input file for reference frames samples"},
-      {"CpmvLogFile", 'l', true, "", "Output files preffix with produced CPMVs"},
-      {"gpus", 0, true, "1", "number of GPUs (POCs frame-sharded over DeviceIndex..+gpus-1)"},
-      {"modes", 0, true, "all", "all = 2- and 3-CP affine, 2cp = 2-CP only"},
-      {"align", 0, true, "both", "both = aligned (FULL) and half-aligned (HALF) CUs, full / half = one of them"},
-      {"threads", 0, true, "0", "host threads for CSV parsing and log formatting (0 = all)"},
-      {"devices", 0, true, "", "explicit device list, e.g. 0,1,2 (overrides DeviceIndex/gpus; "
-                               "a device may repeat: several contexts on one GPU)"},
-  };
-  const int pr = parse(c, argc, argv);
-  if (pr == 1) {
-    print_help(c);
-    return 1;
-  }
-  if (pr == 2) return 1;
-  if (check_report(c) > 0) {
-    printf("Exiting after finding errors in input parameters\n");
-    return 1;
-  }
-  const bool per_launch =
-      std::find(c.flags_set.begin(), c.flags_set.end(), "per-launch") != c.flags_set.end();
-  const std::string modes = c.str("modes");
-  if (modes != "all" && modes != "2cp") {
-    printf("  [!] ERROR: --modes must be all or 2cp\n");
-    return 1;
-  }
-  const std::string align = c.str("align");
-  if (align != "both" && align != "full" && align != "half") {
-    printf("  [!] ERROR: --align must be both, full or half\n");
-    return 1;
-  }
-  const int mode_mask = (modes == "all" ? (VAME_MODE_2CP | VAME_MODE_3CP) : VAME_MODE_2CP) |
-                        (align == "full" ? VAME_MODE_FULL : align == "half" ? VAME_MODE_HALF : 0);
-  const int predMask = vame_pred_mask(mode_mask);  // the PREDs coded, launched and logged
-  const int nthreads = c.num("threads");
-
-  print_timestamp("START HOST");
-
-  // ---- devices (the OpenCL listing of main.cpp:133-247, as HIP)
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
-  for (int d = 0; d < ndev; d++) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, d) != hipSuccess) continue;
-    printf("GPU %d\n\t%s (%s)\n", d, p.name, p.gcnArchName);
-  }
-  std::vector<int> devices;
-  if (!c.str("devices").empty()) {
-    std::stringstream ss(c.str("devices"));
-    for (std::string t; std::getline(ss, t, ',');) devices.push_back(atoi(t.c_str()));
-  } else {
-    for (int g = 0; g < std::max(1, c.num("gpus")); g++) devices.push_back(c.num("DeviceIndex") + g);
-  }
-  const int ngpu = (int)devices.size();
-  for (int d : devices)
-    if (d < 0 || d >= ndev) {
-      printf("Incorrect GPU index. Only %d GPUs are detected\n", ndev);
-      return 0;
-    }
-  for (int d : devices) {
-    hipDeviceProp_t p;
-    (void)hipGetDeviceProperties(&p, d);
-    printf("COMPUTING ON GPU %d\n", d);
-    printf("-- Max compute units %d\n", p.multiProcessorCount);
-  }
-
-  // ---- resolution (main.cpp:285-306)
-  const std::string res = c.str("Resolution");
-  std::vector<std::string> tok;
-  {
-    std::stringstream ss(res);
-    for (std::string t; std::getline(ss, t, 'x');) tok.push_back(t);
-  }
-  if (tok.size() != 2) {
-    printf("  [!] ERROR: Input resolution \"%s\" not set properly\n", res.c_str());
-    return 0;
-  }
-  const int W = atoi(tok[0].c_str()), H = atoi(tok[1].c_str());
-  const int nCtus = vame_num_ctus(W, H);
-  if (nCtus == 0) {
-    printf("[!] ERROR: Unsupported resolution %dx%d\n", W, H);
-    printf("Supported resolutions are:\n");
-    const int rs[5][2] = {{3840, 2160}, {1920, 1080}, {1280, 720}, {832, 480}, {416, 240}};
-    for (auto& r : rs) printf("  %dx%d\n", r[0], r[1]);
-    return 0;
-  }
-  const int N = c.num("FramesToBeEncoded"), qp = c.num("QP"), extra = c.num("ExtraGradientIter");
-  const std::string prefix = c.str("CpmvLogFile");
-  if (N <= 0) {
-    printf("  [!] ERROR: FramesToBeEncoded must be positive\n");
-    return 1;
-  }
-  if (vame_lambda(qp, 1) < 0 || vame_lambda(qp, 8) < 0) {
-    printf("  [!] ERROR: QP %d outside the lambda table\n", qp);
-    return 1;
-  }
-
-  test_references(N, qp);
-
-  // ---- inputs (main.cpp:308-330)
-  const size_t fsz = (size_t)W * H;
-  std::vector<uint16_t> orig(fsz * N), recon(fsz * N);
-  {
-    FILE* a = fopen(c.str("OriginalFrames").c_str(), "r");
-    FILE* b = fopen(c.str("ReferenceFrames").c_str(), "r");
-    if (!a || !b) {
-      perror("error while opening samples files");
-      return 1;
-    }
-    fclose(a);
-    fclose(b);
-  }
+  fclose(a);
+  fclose(b);
   print_timestamp("START READ .csv");
-  const double t_read0 = now_s();
-  if (vame_read_frames(c.str("ReferenceFrames").c_str(), W, H, N, recon.data(), nthreads) ||
-      vame_read_frames(c.str("OriginalFrames").c_str(), W, H, N, orig.data(), nthreads)) {
-    printf("  [!] ERROR: could not read %d frames of %dx%d from the sample files\n", N, W, H);
-    return 1;
+  *t_read0 = now_s();
+  if (vame_read_frames(s.recon_path.c_str(), s.W, s.H, s.frames, recon.data(), s.threads) ||
+      vame_read_frames(s.orig_path.c_str(), s.W, s.H, s.frames, orig.data(), s.threads)) {
+    printf("  [!] ERROR: could not read %d frames of %dx%d from the sample files\n", s.frames, s.W, s.H);
+    return false;
   }
-  const double read_s = now_s() - t_read0;
+  *read_s = now_s() - *t_read0;
   print_timestamp("FINISHED READ .csv");
+  return true;
+}
 
-  printf("Removing older outputs with identical names...\n");  // main.cpp:469 -> :1548
-  vame_log_remove_old(prefix.c_str());
-
-  // ---- shard POCs 1..N over the devices
-  print_timestamp("START ALLOCATE MEMORY");
-  const Layout L(nCtus);
-  Shared S;
-  // per device: two batches in flight plus two POCs' worth for the writer
-  const int per_worker = per_launch ? 3 : 2 * kBatchPocs + 2;
-  std::vector<Slab> slabs((size_t)per_worker * ngpu);
-  S.pools.resize(ngpu);
+// Every worker's pinned slabs, each in its owner's pool.  False after its message.
+bool allocate_slabs(const Settings& s, const Layout& L, std::vector<Slab>& slabs, Shared& S) {
+  const int per_worker = slabs_per_worker(s.per_launch);
+  slabs = std::vector<Slab>((size_t)per_worker * s.devices.size());
+  S.pools.resize(s.devices.size());
   for (size_t i = 0; i < slabs.size(); i++) {
-    Slab& s = slabs[i];
-    if (hipHostMalloc((void**)&s.host, L.bytes, hipHostMallocDefault) != hipSuccess) {
+    Slab& slab = slabs[i];
+    if (hipHostMalloc(slab.block.put(), L.bytes, hipHostMallocDefault) != hipSuccess) {
       printf("  [!] ERROR: pinned host allocation of %zu bytes failed\n", L.bytes);
-      return 1;
+      return false;
     }
-    s.owner = (int)(i / per_worker);
-    S.pools[s.owner].push_back(&s);
+    slab.owner = (int)(i / per_worker);
+    S.pools[slab.owner].push_back(&slab);
   }
-  // Chunks of kBatchPocs consecutive POCs go to the devices in turn.  The writer
-  // takes POCs in order and each device holds at most per_worker unwritten
-  // slabs, so the devices must advance through the sequence together: with one
-  // contiguous block per device, device 1 would stall after its first
-  // per_worker POCs until the writer had drained device 0's whole block.
-  std::vector<Job> jobs(ngpu);
-  for (int p = 1; p <= N; p++) jobs[((p - 1) / kBatchPocs) % ngpu].pocs.push_back(p);
-  print_timestamp("FINISH ALLOCATE MEMORY");
+  return true;
+}
 
-  // the log writer (main.cpp:954-958 -> main_aux_functions.h:387-525) exists
-  // before any worker starts, so a failure here returns with no thread running
-  vame_log_writer* logw = prefix.empty() ? nullptr : vame_log_writer_create(prefix.c_str(), W, H, nthreads);
-  if (!prefix.empty() && !logw) {
-    printf("  [!] ERROR: cannot create the log writer for %s_*\n", prefix.c_str());
-    return 1;
-  }
-
-  print_timestamp("START GPU KERNEL");
-  const double t0 = now_s();
-  std::vector<std::thread> workers;
-  for (int g = 0; g < ngpu; g++) {
-    Job& j = jobs[g];
-    j.worker = g;
-    j.device = devices[g];
-    j.W = W;
-    j.H = H;
-    j.nCtus = nCtus;
-    j.qp = qp;
-    j.extra = extra;
-    j.mode_mask = mode_mask;
-    j.per_launch = per_launch;
-    j.prof = std::find(c.flags_set.begin(), c.flags_set.end(), "prof") != c.flags_set.end();
-    j.orig = orig.data();
-    j.recon = recon.data();
-    j.L = &L;
-    j.S = &S;
-    if (!j.pocs.empty()) workers.emplace_back(gpu_worker, j);
-  }
-
-  // ---- writer: POCs in order (main.cpp:954-958 -> main_aux_functions.h:387-525),
-  // a whole POC per vame_log_writer_poc call (persistent pool, files kept open)
+struct Totals {  // what the writer loop sums over the POCs
   float pred_ns[4] = {0, 0, 0, 0}, fused_ns = 0;
   long long log_bytes = 0;
   double log_s = 0;
+};
+
+// One POC's report lines and log rows, every (refIdx, PRED) in the
+// reference's order.  False after its message.
+bool write_poc(const Settings& s, const Layout& L, vame_log_writer* logw, const Slab& slab, Totals& T) {
+  const int p = slab.poc, predMask = vame_pred_mask(s.mode_mask);
+  const float lambda = vame_lambda(s.qp, p);
+  const int64_t* costs[16] = {};
+  const vame_cpmvs* cps[16] = {};
+  for (int r = 0; r < slab.nrefs; r++) {
+    printf("POC   %d  RefIdx  %d  -> lambda %f\n", p, r, (double)lambda);
+    for (int m = 0; m < 4; m++) {
+      if (!((predMask >> m) & 1)) continue;
+      printf("Reporting results POC=%d refIdx=%d PredType=%d\n", p, r, m);
+      costs[r * 4 + m] = (const int64_t*)(slab.host() + L.off_cost[r][m]);
+      cps[r * 4 + m] = (const vame_cpmvs*)(slab.host() + L.off_cp[r][m]);
+      if (s.prefix.empty() || p != 1 || r != 0) continue;
+      printf("Writing headers\n");
+      if (vame_log_write_headers(s.prefix.c_str(), m)) {
+        printf("  [!] ERROR: cannot create the log files %s_*\n", s.prefix.c_str());
+        return false;
+      }
+    }
+  }
+  if (!logw) return true;
+  const double tl = now_s();
+  const long long nb = vame_log_writer_poc(logw, p, slab.nrefs, predMask, costs, cps);
+  T.log_s += now_s() - tl;
+  if (nb < 0) {
+    printf("  [!] ERROR: writing the log files %s_* failed\n", s.prefix.c_str());
+    return false;
+  }
+  T.log_bytes += nb;
+  return true;
+}
+
+// The writer: POCs in order (main.cpp:954-958 -> main_aux_functions.h:387-525),
+// a whole POC per vame_log_writer_poc call (persistent pool, files kept open),
+// each slab back to its worker's pool.  False if a worker or the writer
+// failed; the workers have then been told to stop.
+bool write_pocs(const Settings& s, const Layout& L, vame_log_writer* logw, Shared& S, Totals& T) {
   bool ok = true;
-  for (int p = 1; p <= N && ok; p++) {
-    Slab* s = nullptr;
+  for (int p = 1; p <= s.frames && ok; p++) {
+    Slab* slab = nullptr;
     {
       std::unique_lock<std::mutex> g(S.mu);
       S.cv.wait(g, [&] { return S.failed || S.done.count(p); });
@@ -867,48 +198,16 @@ int main(int argc, char** argv) {
         ok = false;
         break;
       }
-      s = S.done[p];
+      slab = S.done[p];
       S.done.erase(p);
     }
-    const float lambda = vame_lambda(qp, p);
-    const int64_t* costs[16] = {};
-    const vame_cpmvs* cps[16] = {};
-    for (int r = 0; r < s->nrefs; r++) {
-      printf("POC   %d  RefIdx  %d  -> lambda %f\n", p, r, (double)lambda);
-      for (int m = 0; m < 4; m++) {
-        if (!((predMask >> m) & 1)) continue;
-        printf("Reporting results POC=%d refIdx=%d PredType=%d\n", p, r, m);
-        costs[r * 4 + m] = (const int64_t*)(s->host + L.off_cost[r][m]);
-        cps[r * 4 + m] = (const vame_cpmvs*)(s->host + L.off_cp[r][m]);
-        if (prefix.empty()) continue;
-        if (p == 1 && r == 0) {
-          printf("Writing headers\n");
-          if (vame_log_write_headers(prefix.c_str(), m)) {
-            printf("  [!] ERROR: cannot create the log files %s_*\n", prefix.c_str());
-            ok = false;
-            break;
-          }
-        }
-      }
-      if (!ok) break;
-    }
-    if (ok && logw) {  // the POC's rows, every (refIdx, PRED) in the reference's order
-      const double tl = now_s();
-      const long long nb = vame_log_writer_poc(logw, p, s->nrefs, predMask, costs, cps);
-      log_s += now_s() - tl;
-      if (nb < 0) {
-        printf("  [!] ERROR: writing the log files %s_* failed\n", prefix.c_str());
-        ok = false;
-      } else {
-        log_bytes += nb;
-      }
-    }
-    for (int m = 0; m < 4; m++) pred_ns[m] += s->pred_ns[m];
-    fused_ns += s->fused_ns;
-    memset(s->pred_ns, 0, sizeof s->pred_ns);
-    s->fused_ns = 0;
+    ok = write_poc(s, L, logw, *slab, T);
+    for (int m = 0; m < 4; m++) T.pred_ns[m] += slab->pred_ns[m];
+    T.fused_ns += slab->fused_ns;
+    memset(slab->pred_ns, 0, sizeof slab->pred_ns);
+    slab->fused_ns = 0;
     std::lock_guard<std::mutex> g(S.mu);
-    S.pools[s->owner].push_back(s);
+    S.pools[slab->owner].push_back(slab);
     S.cv.notify_all();
   }
   if (!ok) {
@@ -916,6 +215,80 @@ int main(int argc, char** argv) {
     S.failed = true;
     S.cv.notify_all();
   }
+  return ok;
+}
+
+// main_aux_functions.h:1416-1446 reportTimingResults (ns; float like the reference)
+void report_timing(const Settings& s, Totals& T, double overall, double read_s) {
+  printf("=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=\n");
+  printf("TIMING RESULTS (nanoseconds)\n");
+  float* pred_ns = T.pred_ns;
+  // fused launches: apportion by each PRED's algorithmic work
+  if (!s.per_launch) apportion(T.fused_ns, s.W, s.H, vame_pred_mask(s.mode_mask), s.extra, pred_ns);
+  printf("FULL_2CP_EXEC,%f\n", (double)pred_ns[0]);
+  printf("FULL_3CP_EXEC,%f\n", (double)pred_ns[1]);
+  printf("HALF_2CP_EXEC,%f\n", (double)pred_ns[2]);
+  printf("HALF_3CP_EXEC,%f\n", (double)pred_ns[3]);
+  const double total_ns =
+      s.per_launch ? (double)(pred_ns[0] + pred_ns[1] + pred_ns[2] + pred_ns[3]) : (double)T.fused_ns;
+  printf("TOTAL_EXEC_TIME(%dx),%f\n", s.frames, total_ns);
+  printf("OVERALL(%dx),%f\n", s.frames, (double)(float)overall);
+  if (!s.per_launch) printf("FUSED_POC_EXEC,%f\n", (double)T.fused_ns);
+  // how the four per-PRED keys above were obtained: measured per launch
+  // (--per-launch, the reference's events), or -- one fused launch computes
+  // all four PREDs -- the measured fused time apportioned by algorithmic work
+  printf("PRED_EXEC_SOURCE,%s\n", s.per_launch ? "measured" : "estimated-apportioned");
+  printf("READ_CSV_TIME,%f\n", read_s * 1e9);
+  printf("LOG_WRITE_TIME,%f\n", T.log_s * 1e9);
+  printf("LOG_BYTES,%lld\n", T.log_bytes);
+  printf("=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=\n\n");
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  Settings s;
+  int rc = read_settings(argc, argv, s);
+  if (rc >= 0) return rc;
+  print_timestamp("START HOST");
+  if (!list_devices(s.devices)) return 0;
+  if ((rc = check_settings(s)) >= 0) return rc;
+  test_references(s.frames, s.qp);
+
+  std::vector<uint16_t> orig, recon;
+  double t_read0 = 0, read_s = 0;
+  if (!ingest(s, orig, recon, &t_read0, &read_s)) return 1;
+  printf("Removing older outputs with identical names...\n");  // main.cpp:469 -> :1548
+  vame_log_remove_old(s.prefix.c_str());
+
+  // ---- shard POCs 1..N over the devices.  The slabs are declared before the
+  // workers and outlive them on every return below: no worker is running
+  // when they are freed.
+  print_timestamp("START ALLOCATE MEMORY");
+  const Layout L(vame_num_ctus(s.W, s.H));
+  Shared S;
+  std::vector<Slab> slabs;
+  if (!allocate_slabs(s, L, slabs, S)) return 1;
+  const std::vector<std::vector<int>> pocs = deal_pocs(s.frames, (int)s.devices.size());
+  print_timestamp("FINISH ALLOCATE MEMORY");
+
+  // the log writer (main.cpp:954-958 -> main_aux_functions.h:387-525) exists
+  // before any worker starts, so a failure here returns with no thread running
+  vame_log_writer* logw =
+      s.prefix.empty() ? nullptr : vame_log_writer_create(s.prefix.c_str(), s.W, s.H, s.threads);
+  if (!s.prefix.empty() && !logw) {
+    printf("  [!] ERROR: cannot create the log writer for %s_*\n", s.prefix.c_str());
+    return 1;
+  }
+
+  print_timestamp("START GPU KERNEL");
+  const double t0 = now_s();
+  std::vector<std::thread> workers;
+  for (int g = 0; g < (int)s.devices.size(); g++)
+    if (!pocs[g].empty())
+      workers.emplace_back(gpu_worker, Job{g, s.devices[g], pocs[g], &s, orig.data(), recon.data(), &L, &S});
+  Totals T;
+  const bool ok = write_pocs(s, L, logw, S, T);
   for (auto& t : workers) t.join();
   if (logw) vame_log_writer_destroy(logw);
   fflush(stdout);
@@ -925,40 +298,11 @@ int main(int argc, char** argv) {
   }
   print_timestamp("FINISH GPU KERNEL");
   const double overall = now_s() - t0;
-  if (getenv("VAME_CLI_TRACE") && atoi(getenv("VAME_CLI_TRACE")) != 0)
+  if (trace_enabled())
     fprintf(stderr, "[trace] workers started %.1f ms after reading; overall %.1f ms, log writing %.1f ms\n",
-            (t0 - t_read0 - read_s) * 1e3, overall * 1e3, log_s * 1e3);
-
-  // main_aux_functions.h:1416-1446 reportTimingResults (ns; float like the reference)
-  printf("=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=\n");
-  printf("TIMING RESULTS (nanoseconds)\n");
-  if (!per_launch) {  // fused launches: apportion by each PRED's algorithmic work
-    double wgt[4], sum = 0;
-    for (int m = 0; m < 4; m++) {
-      wgt[m] = !((predMask >> m) & 1) ? 0 : pred_work(W, H, m >> 1, (m & 1) ? 3 : 2, extra);
-      sum += wgt[m];
-    }
-    for (int m = 0; m < 4; m++) pred_ns[m] = (float)((double)fused_ns * wgt[m] / sum);
-  }
-  printf("FULL_2CP_EXEC,%f\n", (double)pred_ns[0]);
-  printf("FULL_3CP_EXEC,%f\n", (double)pred_ns[1]);
-  printf("HALF_2CP_EXEC,%f\n", (double)pred_ns[2]);
-  printf("HALF_3CP_EXEC,%f\n", (double)pred_ns[3]);
-  const double total_ns = per_launch ? (double)(pred_ns[0] + pred_ns[1] + pred_ns[2] + pred_ns[3])
-                                     : (double)fused_ns;
-  printf("TOTAL_EXEC_TIME(%dx),%f\n", N, total_ns);
-  printf("OVERALL(%dx),%f\n", N, (double)(float)overall);
-  if (!per_launch) printf("FUSED_POC_EXEC,%f\n", (double)fused_ns);
-  // how the four per-PRED keys above were obtained: measured per launch
-  // (--per-launch, the reference's events), or -- one fused launch computes
-  // all four PREDs -- the measured fused time apportioned by algorithmic work
-  printf("PRED_EXEC_SOURCE,%s\n", per_launch ? "measured" : "estimated-apportioned");
-  printf("READ_CSV_TIME,%f\n", read_s * 1e9);
-  printf("LOG_WRITE_TIME,%f\n", log_s * 1e9);
-  printf("LOG_BYTES,%lld\n", log_bytes);
-  printf("=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=-=\n\n");
-
-  for (auto& s : slabs) (void)hipHostFree(s.host);
+            (t0 - t_read0 - read_s) * 1e3, overall * 1e3, T.log_s * 1e3);
+  report_timing(s, T, overall, read_s);
+  slabs.clear();
   print_timestamp("FINISH HOST");
   return 0;
 }

@@ -13,6 +13,7 @@ import hashlib
 import os
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -179,10 +180,6 @@ def test_gathered_logs_byte_identical(seq, world):
     assert len(compare_dirs(run_ranks(seq, world, f"gather{world}", ["--gather-records"]), seq / "expected")) == 40
 
 
-def self_gather_worker(rank, world, port, argv, table_path):
-    rank_worker(rank, world, port, argv, table_path)
-
-
 @pytest.mark.timeout(600)
 def test_one_rank_group_gathers_its_own_records(seq):
     """A one-rank process group (what VAME_FORCE_PG=1 forms): rank 0's records
@@ -195,7 +192,7 @@ def test_one_rank_group_gathers_its_own_records(seq):
             "-o", str(seq / "orig.csv"), "-r", str(seq / "recon.csv"), "-l", str(out / "log"),
             "--gather-records"]
     from vame.launch import free_port
-    mp.spawn(self_gather_worker, args=(1, free_port(), argv, str(seq / "table.pt")), nprocs=1, join=True)
+    mp.spawn(rank_worker, args=(1, free_port(), argv, str(seq / "table.pt")), nprocs=1, join=True)
     assert len(compare_dirs(out, seq / "expected")) == 40
 
 
@@ -456,3 +453,209 @@ def test_eight_ranks_cut_pocs_and_long_term_refs(tmp_path):
     for name, extra in (("gather8", ("--gather-records",)), ("shard8", ())):
         mp.spawn(fake_worker, args=(8, free_port(), argv(tmp_path / name, *extra)), nprocs=8, join=True)
         assert len(compare_dirs(tmp_path / name, one)) == 20, name
+
+
+# ---- who writes what (logs.log_role), and every way out of run_rank
+
+R = logs.LogRole
+APPEND = dict(remove_old=True, writer="append", download=True)  # rank 0 of any run that writes
+ROLE_TABLE = [  # (case, (log, log_path, world, rank, grouped, merge), the role read off the unsplit run_rank)
+    ("no -l", ("", "place", 2, 1, True, False), R()),
+    ("no -l, gather", ("", "gather", 3, 0, True, False), R()),
+    ("one rank, no group", ("L", "place", 1, 0, False, False), R(prefix="L", **APPEND)),
+    ("one rank, no group, --gather-records", ("L", "gather", 1, 0, False, False), R(prefix="L", **APPEND)),
+    ("one-rank group, --gather-records", ("L", "gather", 1, 0, True, False),
+     R(prefix="L", remove_old=True, writer="append", pack=True, gather=True, unpack_own=True)),
+    ("gather, rank 0", ("L", "gather", 3, 0, True, False), R(prefix="L", gather=True, **APPEND)),
+    ("gather, rank 2", ("L", "gather", 3, 2, True, False), R(prefix="L", pack=True, gather=True)),
+    ("place, rank 0", ("L", "place", 3, 0, True, False), R(prefix="L", exchange=True, barrier=True, **APPEND)),
+    ("place, rank 2", ("L", "place", 3, 2, True, False),
+     R(prefix="L", writer="deferred", download=True, exchange=True, place=True, barrier=True)),
+    ("parts, rank 0", ("L", "parts", 3, 0, True, False), R(prefix="L", barrier=True, **APPEND)),
+    ("parts, rank 2", ("L", "parts", 3, 2, True, False), R(prefix="L.part2", barrier=True, **APPEND)),
+    ("parts --merge-parts, rank 0", ("L", "parts", 3, 0, True, True),
+     R(prefix="L", barrier=True, merge=True, **APPEND)),
+    ("parts --merge-parts, rank 2", ("L", "parts", 3, 2, True, True),
+     R(prefix="L.part2", barrier=True, **APPEND)),
+    ("--rank-only 0, place", ("L", "place", 2, 0, False, False), R(prefix="L", **APPEND)),
+    ("--rank-only 1, place", ("L", "place", 2, 1, False, False),
+     R(prefix="L.part1", remove_old=True, writer="deferred", download=True, place=True)),
+    ("--rank-only 0, parts", ("L", "parts", 2, 0, False, False), R(prefix="L", **APPEND)),
+    ("--rank-only 1, parts", ("L", "parts", 2, 1, False, False), R(prefix="L.part1", **APPEND)),
+]
+
+
+@pytest.mark.parametrize("case,args,want", ROLE_TABLE, ids=[c[0] for c in ROLE_TABLE])
+def test_log_role_table(case, args, want):
+    """log_role against the roles read off the unsplit run_rank's expressions
+    (gather_path, self_gather, writes_own, prefix, the remove_old / LogWriter /
+    defer conditions and the end phase's chain); and the ranks of a world agree
+    on every collective, so none waits for a rank that skipped it."""
+    log, path, world, rank, grouped, merge = args
+    assert logs.log_role(*args) == want
+    assert distrun.part_prefix("L", 2) == "L.part2"
+    roles = [logs.log_role(log, path, world, r, grouped, merge) for r in range(world)]
+    assert len({(x.gather, x.exchange, x.barrier) for x in roles}) == 1
+    if not grouped:
+        assert not any(x.gather or x.exchange or x.barrier for x in roles)
+    assert all(x.download != x.pack for x in roles) if log else not any(x.download or x.pack for x in roles)
+    assert sum(x.merge for x in roles) <= 1 and all((x.writer == "deferred") == x.place for x in roles)
+
+
+FAKE = dict(W=416, H=240, n=6, qp=27)
+
+
+def fake_argv(tmp, out, *extra):
+    return ["-f", str(FAKE["n"]), "-s", f"{FAKE['W']}x{FAKE['H']}", "-q", str(FAKE["qp"]),
+            "-o", str(tmp / "orig.csv"), "-r", str(tmp / "recon.csv"), "-l", str(out / "log"), "--modes", "2cp",
+            "--gpus", "2", "--rank-only", "1", *extra]
+
+
+def part_files(out, rank=1):
+    pre = os.path.basename(logs.part_prefix("log", rank)) + "_"
+    return {f: (out / f).read_bytes() for f in sorted(os.listdir(out)) if f.startswith(pre)}
+
+
+@pytest.fixture(scope="module")
+def fake_seq(tmp_path_factory):
+    """The 6-POC CSVs and rank 1 of 2's part files from a clean run (FakeEngine)."""
+    tmp = tmp_path_factory.mktemp("fake")
+    orig, recon = synth_sequence(FAKE["W"], FAKE["H"], FAKE["n"], FAKE["qp"], seed=21)
+    write_csv(str(tmp / "orig.csv"), orig)
+    write_csv(str(tmp / "recon.csv"), recon)
+    (tmp / "clean").mkdir()
+    a = distrun.parse_args(fake_argv(tmp, tmp / "clean"))
+    distrun.run_rank(a, 2, 1, FakeEngine(a.W, a.H), torch.device("cpu"))
+    assert len(part_files(tmp / "clean")) == 20
+    return tmp
+
+
+class FailingEngine(FakeEngine):
+    """Its second launch raises `self.boom`."""
+
+    def __init__(self, W, H):
+        super().__init__(W, H)
+        self.calls, self.boom = 0, RuntimeError("boom")
+
+    def affine_me_batch(self, jobs, modes, extra):
+        self.calls += 1
+        if self.calls == 2:
+            raise self.boom
+        return super().affine_me_batch(jobs, modes, extra)
+
+
+def raising_on_call(fn, k, exc):
+    calls = [0]
+
+    def wrapped(*args, **kw):
+        calls[0] += 1
+        if calls[0] == k:
+            raise exc
+        return fn(*args, **kw)
+    return wrapped
+
+
+def run_rank_expecting(monkeypatch, tmp, out, engine, exc, extra=()):
+    """run_rank as rank 1 of 2 alone (overlapped ingest, three launches) must
+    raise exactly `exc`, leave no thread behind and close every LogWriter."""
+    monkeypatch.setenv("VAME_FIRST_LAUNCH_PAIRS", "1")
+    made = []
+
+    class Counted(logs.LogWriter):
+        def __init__(self, *args, **kw):
+            self.closes = 0
+            made.append(self)
+            super().__init__(*args, **kw)
+
+        def close(self):
+            self.closes += 1
+            super().close()
+    monkeypatch.setattr(logs, "LogWriter", Counted)
+    a = distrun.parse_args(fake_argv(tmp, out, *extra))
+    assert len(distrun.launch_batches(shard.pair_shard(a.frames, 2, 1), 1)) == 3
+    before = set(threading.enumerate())
+    with pytest.raises(type(exc)) as caught:
+        distrun.run_rank(a, 2, 1, engine, torch.device("cpu"))
+    assert caught.value is exc
+    assert set(threading.enumerate()) <= before
+    assert len(made) == 1 and all(w.closes >= 1 and w._w is None for w in made)
+
+
+@pytest.mark.timeout(60)
+@pytest.mark.parametrize("path", ["place", "parts"])
+def test_engine_failure_unwinds(monkeypatch, fake_seq, tmp_path, path):
+    eng = FailingEngine(FAKE["W"], FAKE["H"])
+    run_rank_expecting(monkeypatch, fake_seq, tmp_path, eng, eng.boom, ["--shard-logs"] * (path == "parts"))
+    assert eng.calls == 2
+
+
+@pytest.mark.timeout(60)
+def test_uploader_failure_unwinds(monkeypatch, fake_seq, tmp_path):
+    """The third read_frames call is launch 1's first, in the uploader thread."""
+    exc = RuntimeError("no frames")
+    monkeypatch.setattr(logs, "read_frames", raising_on_call(logs.read_frames, 3, exc))
+    run_rank_expecting(monkeypatch, fake_seq, tmp_path, FakeEngine(FAKE["W"], FAKE["H"]), exc)
+
+
+@pytest.mark.timeout(60)
+def test_writer_failure_unwinds(monkeypatch, fake_seq, tmp_path):
+    """The second write_poc call is launch 1's POC, in the writer thread."""
+    exc = RuntimeError("disk full")
+    monkeypatch.setattr(logs, "write_poc", raising_on_call(logs.write_poc, 2, exc))
+    run_rank_expecting(monkeypatch, fake_seq, tmp_path, FakeEngine(FAKE["W"], FAKE["H"]), exc)
+
+
+@pytest.mark.timeout(60)
+def test_deferred_writer_failure_leaves_no_stale_rows(monkeypatch, fake_seq, tmp_path):
+    """The place path's rank 1 holds its rows until the end: a run that fails
+    before then leaves its part files as remove_old left them (none, and none
+    of the stale bytes), and the next clean run writes the clean run's bytes."""
+    clean = part_files(fake_seq / "clean")
+    for f in clean:  # stale, longer than any real part
+        (tmp_path / f).write_bytes(b"X" * 1_000_000)
+    eng = FailingEngine(FAKE["W"], FAKE["H"])
+    run_rank_expecting(monkeypatch, fake_seq, tmp_path, eng, eng.boom)
+    assert all(b"X" * 64 not in v for v in part_files(tmp_path).values())
+    a = distrun.parse_args(fake_argv(fake_seq, tmp_path))
+    distrun.run_rank(a, 2, 1, FakeEngine(a.W, a.H), torch.device("cpu"))
+    assert part_files(tmp_path) == clean
+
+
+# ---- MI355X: the part-file paths on the device
+
+@pytest.fixture(scope="module")
+def gpu_small(tmp_path_factory):
+    """416x240, 7 POCs: the CSVs and the single-process CLI's 40 files."""
+    tmp = tmp_path_factory.mktemp("gpu_small")
+    orig, recon = synth_sequence(416, 240, 7, qp=32, seed=9)
+    write_csv(str(tmp / "orig.csv"), orig)
+    write_csv(str(tmp / "recon.csv"), recon)
+    run_cli(tmp, 416, 240, 7, 32)
+    return tmp
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_distrun_shard_logs_merged_equals_cli(gpu_small):
+    """`--gpus 2 --shard-logs --merge-parts`: rank 1 appends to its part files
+    as its launches complete, rank 0 appends them to the final files after the
+    barrier; the 40 files are the CLI's byte for byte and no part is left."""
+    out, stdout = run_distrun_gpu(gpu_small, 416, 240, 7, 32, "parts_merged",
+                                  ("--gpus", "2", "--shard-logs", "--merge-parts"))
+    assert len(compare_dirs(out, gpu_small / "cli")) == 40
+    assert '"log_path": "parts"' in stdout and '"ranks": 2' in stdout
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_distrun_rank_only_part_files_equal_the_shard_runs(gpu_small):
+    """`--gpus 2 --rank-only 1`, held and placed at offset 0 (default) or
+    appended as it goes (--shard-logs), writes the part files rank 1 of a
+    `--gpus 2 --shard-logs` run writes."""
+    both, _ = run_distrun_gpu(gpu_small, 416, 240, 7, 32, "parts", ("--gpus", "2", "--shard-logs"))
+    want = part_files(both)
+    assert len(want) == 40 and len(os.listdir(both)) == 80
+    for name, extra in (("only_place", ()), ("only_parts", ("--shard-logs",))):
+        out, _ = run_distrun_gpu(gpu_small, 416, 240, 7, 32, name, ("--gpus", "2", "--rank-only", "1", *extra))
+        assert sorted(os.listdir(out)) == sorted(want), name
+        assert part_files(out) == want, name

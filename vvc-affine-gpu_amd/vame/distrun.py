@@ -125,6 +125,187 @@ def launch_batches(blocks, first: int = MAX_PAIRS):
     return out
 
 
+@contextlib.contextmanager
+def _owned(*steps):
+    """A scope that releases what it started: on every way out each of `steps`
+    runs, in order, whatever the ones before it did.  The first error -- the
+    body's, else the first a step raised -- is the one raised; a later one
+    never replaces it."""
+    err = None
+    try:
+        yield
+    except BaseException as e:  # raised again below, after the steps
+        err = e
+    for step in steps:
+        try:
+            step()
+        except BaseException as e:  # kept only if it is the first
+            err = err or e
+    if err is not None:
+        raise err
+
+
+class _Streams:
+    """The caller's compute stream and the two copy streams of a rank (all None
+    on a CPU rank).  Frames go up and results come back on streams of their
+    own, and those take an explicit priority (VAME_COPY_PRIO, default -1): HIP
+    maps streams onto 4 hardware queues in creation order, and a copy stream
+    sharing the compute stream's queue puts each launch's result download in
+    front of the next launch (the vame CLI measured 5.1 ms of idle GPU per
+    4-POC 4K launch that way).  So: upload before download, both before the
+    first launch, and no other stream."""
+
+    def __init__(self, device):
+        self.device, self.cuda = device, device.type == "cuda"
+        self.compute = self.up = self.down = None
+        if self.cuda:
+            prio = int(os.environ.get("VAME_COPY_PRIO", "-1"))
+            self.compute = torch.cuda.current_stream(device)
+            self.up = torch.cuda.Stream(device, priority=prio)
+            self.down = torch.cuda.Stream(device, priority=prio)
+
+    def on(self, stream):
+        return torch.cuda.stream(stream) if self.cuda else contextlib.nullcontext()
+
+    def synchronize(self) -> None:
+        """Wait for everything the rank has queued on its device."""
+        if self.cuda:
+            torch.cuda.synchronize(self.device)
+
+
+class Ingest:
+    """Frame ingest: only the frames this block reads (main.cpp:293-330).
+    Text lines have no fixed length, so the ranks first index the CSVs
+    together: rank r counts the newlines of chunks r, r + N, ... and one
+    all_reduce shares the counts; each rank then parses only the chunks that
+    hold its frames.  With the line index, each launch's frames are parsed just
+    before they go up, by the uploader thread (`read_launch`), so the GPU starts
+    after the first launch's frames only and the rest of the ingest runs beside
+    the kernels (the reference reads every frame first); without it (a one-rank
+    run, raw frames) the block's frames are read at once, here."""
+
+    def __init__(self, a, world: int, rank: int, dist, blocks):
+        t = time.perf_counter()
+        self.W, self.H, self.paths = a.W, a.H, (a.orig, a.recon)
+        self.orig, self.recon = {}, {}  # host frames by POC
+        self.parse_s = 0.0  # time in read_into: the uploader thread's once it runs
+        self.T = {}  # index_others_s (--rank-only), index_s, read_csv_s
+        self.idx = {path: line_index(path, world, rank, dist, self.T) for path in self.paths}
+        others = self.T.get("index_others_s", 0.0)
+        self.T["index_s"] = time.perf_counter() - t - others
+        self.overlap = bool(blocks) and all(i is not None for i in self.idx.values())
+        if blocks and not self.overlap:
+            self.read_launch(blocks)
+        self.T["read_csv_s"] = time.perf_counter() - t - others
+
+    def read_into(self, store: dict, path: str, frames) -> None:
+        """Parse `frames` (POC numbers, 0-based frame index in the file) of
+        `path` into `store`, one contiguous run of frames per read."""
+        frames = sorted(f for f in set(frames) if f not in store)
+        t0 = time.perf_counter()
+        k = 0
+        while k < len(frames):
+            e = k
+            while e + 1 < len(frames) and frames[e + 1] == frames[e] + 1:
+                e += 1
+            first, n = frames[k], frames[e] - frames[k] + 1
+            idx = self.idx[path]
+            span = None if idx is None else logs.line_span(*idx, first * self.H, (first + n) * self.H)
+            got = logs.read_frames(path, self.W, self.H, n, first=first, span=span)
+            for i in range(n):
+                store[first + i] = got[i]
+            k = e + 1
+        self.parse_s += time.perf_counter() - t0
+
+    def read_launch(self, batch) -> None:
+        """The frames the pairs of `batch` read."""
+        self.read_into(self.orig, self.paths[0], [p - 1 for p, _ in batch])
+        self.read_into(self.recon, self.paths[1], [ref_list(p)[r] for p, refs in batch for r in refs])
+
+    def drop_through(self, poc: int) -> None:
+        """Forget the original frames of POCs up to `poc` (no later launch reads them)."""
+        for q in [q for q in self.orig if q + 1 <= poc]:
+            del self.orig[q]
+
+
+class Uploader:
+    """Frames go to the device launch by launch, ahead of the kernels, from a
+    thread and on a stream of their own (copies from pageable memory block the
+    calling thread, so the launching thread never waits for them); the compute
+    stream waits for each launch's upload event (`wait`)."""
+
+    def __init__(self, ingest: Ingest, batches, streams: _Streams, t_start: float):
+        self.ingest, self.batches, self.streams, self.t_start = ingest, batches, streams, t_start
+        self.d_orig, self.d_recon = {}, {}  # device frames by POC
+        self.ready = [threading.Event() for _ in batches]
+        self.events = [None] * len(batches)
+        self.error = None  # what the thread raised
+        self.first_frames_s = None  # launch 0's frames parsed, since t_start (overlapped ingest)
+        self._halt = threading.Event()
+        self._thread = threading.Thread(target=self._run, name="vame-distrun-uploader")
+
+    def start(self) -> None:
+        self._thread.start()
+
+    def stop_and_join(self) -> None:
+        self._halt.set()
+        if self._thread.ident is not None:
+            self._thread.join()
+
+    def wait(self, b: int):
+        """Block until launch b's frames are queued; its upload event (None on
+        a CPU rank).  Raises what the thread raised."""
+        self.ready[b].wait()
+        if self.error is not None:
+            raise self.error
+        return self.events[b]
+
+    def frames(self, poc: int, refs):
+        """(current frame, [reference frames]) of one entry, on the device."""
+        rl = ref_list(poc)
+        return self.d_orig[poc], [self.d_recon[rl[r]] for r in refs]
+
+    def _run(self) -> None:
+        s = self.streams
+        try:
+            with (torch.cuda.device(s.device) if s.cuda else contextlib.nullcontext()), s.on(s.up):
+                for b, batch in enumerate(self.batches):
+                    if self._halt.is_set():
+                        break
+                    self._upload(b, batch)
+        except Exception as e:  # surfaced by the launching thread (wait)
+            self.error = e
+        finally:
+            for ev in self.ready:
+                ev.set()
+
+    def _upload(self, b: int, batch) -> None:
+        ing, s = self.ingest, self.streams
+        if ing.overlap:  # this launch's frames, parsed now
+            ing.read_launch(batch)
+            if b == 0:
+                self.first_frames_s = time.perf_counter() - self.t_start
+        for poc, refs in batch:
+            rl = ref_list(poc)
+            self._frame(self.d_orig, poc, ing.orig[poc - 1])
+            for r in refs:
+                self._frame(self.d_recon, rl[r], ing.recon[rl[r]])
+        if ing.overlap:
+            ing.drop_through(max(p for p, _ in batch))
+        if s.cuda:
+            self.events[b] = torch.cuda.Event()
+            self.events[b].record(s.up)
+        self.ready[b].set()
+
+    def _frame(self, store: dict, key: int, host) -> None:
+        if key not in store:
+            t = torch.from_numpy(np.ascontiguousarray(host).view(np.int16))
+            if self.streams.cuda:
+                t = t.to(self.streams.device, non_blocking=True)
+                t.record_stream(self.streams.compute)
+            store[key] = t
+
+
 class _HostSlots:
     """Pinned host copies of the results of a launch, one set per slot
     (reused when the writer has finished with it)."""
@@ -144,307 +325,274 @@ class _HostSlots:
         return b
 
 
-def run_rank(a, world: int, rank: int, engine, device, dist=None) -> dict:
-    """One rank's whole run; returns its timings.  `engine` needs n_cus,
-    alloc_poc and affine_me_batch (vame.engine.Engine on the GPU; the tests
-    pass an oracle-backed stand-in on CPU ranks)."""
-    t_start = time.perf_counter()
-    W, H, modes = a.W, a.H, a.mode_mask
-    n_cus = (engine.n_cus(0), engine.n_cus(1))
-    cuda = device.type == "cuda"
-    blocks = shard.pair_shard(a.frames, world, rank)
-    T = {"rank": rank, "pairs": sum(len(r) for _, r in blocks), "pocs": len(blocks),
-         "read_csv_s": 0.0, "kernel_s": 0.0, "log_write_s": 0.0, "log_bytes": 0, "gather_s": 0.0,
-         "merge_s": 0.0}
+def host_records(refs, res) -> dict:
+    """One entry's records as `logs.write_poc` takes them: keyed by the true
+    refIdx (refs[j]; `res` is keyed by the index within the entry), numpy."""
+    return {(refs[j], name): (c.cpu().numpy(), p.cpu().numpy()) for (j, name), (c, p) in res.items()}
 
-    def barrier():
-        if dist is not None:
-            dist.barrier()
 
-    # ---- frame ingest: only the frames this block reads (main.cpp:293-330).
-    # Text lines have no fixed length, so the ranks first index the CSVs
-    # together: rank r counts the newlines of chunks r, r + N, ... and one
-    # all_reduce shares the counts; each rank then parses only the chunks that
-    # hold its frames.
-    # With the line index, each launch's frames are parsed just before they go
-    # up, in the uploader thread (below), so the GPU starts after the first
-    # launch's frames only and the rest of the ingest runs beside the kernels
-    # (the reference reads every frame first, main.cpp:293-330); without it (a
-    # one-rank run, raw frames) the block's frames are read at once, here.
-    t = time.perf_counter()
-    idx = {path: line_index(path, world, rank, dist, T) for path in (a.orig, a.recon)}
-    T["index_s"] = time.perf_counter() - t - T.get("index_others_s", 0.0)
-    d_orig, d_recon = {}, {}
-    orig, recon = {}, {}  # host frames by POC
-    pocs = [p for p, _ in blocks]
-    need = sorted({ref_list(p)[r] for p, refs in blocks for r in refs})
-    parse_s = [0.0]
+class LogSink:
+    """Where a rank's records go on the host: its LogWriter (if `role` gives it
+    one), the two pinned slots each launch's results are copied into on the
+    download stream while the GPU runs the next launch, and the writer thread
+    that formats a launch's POCs once its copy has landed."""
 
-    def read_into(store, path, frames):
-        """Parse `frames` (POC numbers, 0-based frame index in the file) of
-        `path` into `store`, one contiguous run of frames per read."""
-        frames = sorted(f for f in set(frames) if f not in store)
-        t0 = time.perf_counter()
-        k = 0
-        while k < len(frames):
-            e = k
-            while e + 1 < len(frames) and frames[e + 1] == frames[e] + 1:
-                e += 1
-            first, n = frames[k], frames[e] - frames[k] + 1
-            span = None if idx[path] is None else logs.line_span(*idx[path], first * H, (first + n) * H)
-            got = logs.read_frames(path, W, H, n, first=first, span=span)
-            for i in range(n):
-                store[first + i] = got[i]
-            k = e + 1
-        parse_s[0] += time.perf_counter() - t0
+    def __init__(self, role: logs.LogRole, W: int, H: int, streams: _Streams):
+        self.role, self.W, self.H, self.streams = role, W, H, streams
+        self.writer = None
+        self.slots = _HostSlots(2, streams.cuda)
+        self.work: queue.Queue = queue.Queue()
+        self.error = None  # what the thread raised
+        self.log_bytes, self.log_write_s = 0, 0.0  # the thread's until it is joined, then the caller's
+        self._thread = threading.Thread(target=self._run, name="vame-distrun-log-writer")
 
-    overlap = blocks and idx[a.orig] is not None and idx[a.recon] is not None
-    if blocks and not overlap:
-        read_into(orig, a.orig, [p - 1 for p in pocs])
-        read_into(recon, a.recon, need)
-    T["read_csv_s"] = time.perf_counter() - t - T.get("index_others_s", 0.0)
+    def open(self) -> None:
+        """Remove old files, create the writer, start the thread."""
+        if self.role.remove_old:
+            logs.remove_old(self.role.prefix)
+        if self.role.writer != "none":
+            self.writer = logs.LogWriter(self.role.prefix, self.W, self.H)
+            if self.role.writer == "deferred":
+                self.writer.defer()
+        self._thread.start()
 
-    # frames go to the device launch by launch, ahead of the kernels, from a
-    # thread and on a stream of their own (copies from pageable memory block
-    # the calling thread, so the launching thread never waits for them); the
-    # compute stream waits for each launch's upload event.  Results come back
-    # on a third stream, overlapping the next launch.  The copy streams take an
-    # explicit priority (VAME_COPY_PRIO, default -1): HIP maps streams onto 4
-    # hardware queues, and a copy stream sharing the compute stream's queue
-    # puts each launch's result download in front of the next launch (the
-    # vame CLI measured 5.1 ms of idle GPU per 4-POC 4K launch that way).
-    batches = list(launch_batches(blocks, int(os.environ.get("VAME_FIRST_LAUNCH_PAIRS", "8")) if overlap
-                                  else MAX_PAIRS))
-    compute = torch.cuda.current_stream(device) if cuda else None
-    prio = int(os.environ.get("VAME_COPY_PRIO", "-1"))
-    upstream = torch.cuda.Stream(device, priority=prio) if cuda else None
-    dnstream = torch.cuda.Stream(device, priority=prio) if cuda else None
-    up_ready = [threading.Event() for _ in batches]
-    up_ev = [None] * len(batches)
-    up_err, up_stop = [], threading.Event()
+    def write(self, poc: int, refs, res) -> None:
+        self.log_bytes += logs.write_poc(self.role.prefix, self.W, self.H, poc, host_records(refs, res),
+                                         writer=self.writer)
 
-    def uploader():
-        def frame(store, key, host):
-            if key not in store:
-                t = torch.from_numpy(np.ascontiguousarray(host).view(np.int16))
-                if cuda:
-                    t = t.to(device, non_blocking=True)
-                    t.record_stream(compute)
-                store[key] = t
+    def _run(self) -> None:
         try:
-            with (torch.cuda.device(device) if cuda else contextlib.nullcontext()), \
-                    (torch.cuda.stream(upstream) if cuda else contextlib.nullcontext()):
-                for b, batch in enumerate(batches):
-                    if up_stop.is_set():
-                        break
-                    if overlap:  # this launch's frames, parsed now
-                        read_into(orig, a.orig, [p - 1 for p, _ in batch])
-                        read_into(recon, a.recon, [ref_list(p)[r] for p, refs in batch for r in refs])
-                        if b == 0:
-                            T["first_frames_s"] = time.perf_counter() - t_start
-                    for poc, refs in batch:
-                        rl = ref_list(poc)
-                        frame(d_orig, poc, orig[poc - 1])
-                        for r in refs:
-                            frame(d_recon, rl[r], recon[rl[r]])
-                    if overlap:  # host frames no later launch reads
-                        last = max(p for p, _ in batch)
-                        for q in [q for q in orig if q + 1 <= last]:
-                            del orig[q]
-                    if cuda:
-                        up_ev[b] = torch.cuda.Event()
-                        up_ev[b].record(upstream)
-                    up_ready[b].set()
-        except Exception as e:  # surfaced by the launching thread
-            up_err.append(e)
-        finally:
-            for ev in up_ready:
-                ev.set()
-
-    up_th = threading.Thread(target=uploader, daemon=True)
-    up_th.start()
-
-    # ---- who writes what: rank 0 appends to the final files as it goes; by
-    # default every other rank formats its block into host memory (a deferred
-    # writer) and places it into the same files at the end; with --shard-logs
-    # it appends to its own part files as it goes.  In a one-rank process group
-    # (VAME_FORCE_PG) rank 0's own records take the gather path too, so the
-    # collective and the writing from gathered slabs run on one GPU.
-    path = a.log_path
-    gather_path = bool(a.log) and path == "gather" and dist is not None
-    self_gather = gather_path and world == 1
-    writes_own = bool(a.log) and (rank == 0 or path != "gather") and not self_gather
-    # --rank-only K (no group) and --shard-logs: rank K's rows in part files
-    prefix = a.log if rank == 0 or (dist is not None and path != "parts") else part_prefix(a.log, rank)
-    if a.log and (rank == 0 or dist is None or path == "parts"):
-        # removeOldTraces (main.cpp:469); part files too: the deferred writer
-        # places its rows at offsets without truncating, the part writer appends
-        logs.remove_old(prefix)
-    writer = logs.LogWriter(prefix, W, H) if (writes_own or (self_gather and rank == 0)) else None
-    if writer is not None and rank > 0 and path == "place":
-        writer.defer()
-    slab_parts = []
-    # the compact-form check of the packed records, collected on the device and
-    # read once after the last launch (a per-launch read would stall the
-    # launching thread until that launch finished)
-    hip_pack = hasattr(engine, "pack_records")  # the HIP engine packs in one kernel
-    pack_bad = torch.zeros((), dtype=torch.int32 if hip_pack else torch.bool, device=device)
-
-    # ---- the writer thread: formats each launch's POCs once its copy landed
-    slots = _HostSlots(2, cuda)
-    work: queue.Queue = queue.Queue()
-    err = []
-
-    def writer_loop():
-        try:
-            while True:
-                item = work.get()
-                if item is None:
-                    return
+            while (item := self.work.get()) is not None:
                 ev, slot, batch, host = item
                 if ev is not None:
                     ev.synchronize()
                 t0 = time.perf_counter()
                 for (poc, refs), res in zip(batch, host):
-                    results = {(refs[j], name): (c.numpy(), p.numpy()) for (j, name), (c, p) in res.items()}
-                    T["log_bytes"] += logs.write_poc(prefix, W, H, poc, results, writer=writer)
-                T["log_write_s"] += time.perf_counter() - t0
-                slots.free.put(slot)
-        except Exception as e:  # surfaced after the join
-            err.append(e)
-            slots.free.put(-1)
+                    self.write(poc, refs, res)
+                self.log_write_s += time.perf_counter() - t0
+                self.slots.free.put(slot)
+        except Exception as e:  # surfaced by end_and_join
+            self.error = e
+            self.slots.free.put(-1)
 
-    th = threading.Thread(target=writer_loop, daemon=True)
-    th.start()
+    def download(self, batch, outs) -> bool:
+        """Queue the copy of one launch's results into a free slot and hand it
+        to the thread; False once the thread has failed."""
+        slot = self.slots.free.get()
+        if slot < 0:
+            return False
+        s, host = self.streams, []
+        if s.cuda:
+            s.down.wait_stream(torch.cuda.current_stream(s.device))
+        with s.on(s.down):
+            for i, out in enumerate(outs):
+                h = {}
+                for key, (c, p) in out.items():
+                    hc = self.slots.host_like(slot, (i, key, 0), c)
+                    hp = self.slots.host_like(slot, (i, key, 1), p)
+                    hc.copy_(c, non_blocking=s.cuda)
+                    hp.copy_(p, non_blocking=s.cuda)
+                    if s.cuda:  # the launch's buffers stay allocated until the copy ran
+                        c.record_stream(s.down)
+                        p.record_stream(s.down)
+                    h[key] = (hc, hp)
+                host.append(h)
+            ev = None
+            if s.cuda:
+                ev = torch.cuda.Event()
+                ev.record(s.down)
+        self.work.put((ev, slot, batch, host))
+        return True
 
-    # ---- the hot path: this block's launches
+    def end_and_join(self) -> None:
+        """Let the thread finish what is queued; raises what it raised."""
+        if self._thread.ident is not None:
+            self.work.put(None)
+            self._thread.join()
+        if self.error is not None:
+            raise self.error
+
+    def close(self) -> None:
+        if self.writer is not None:
+            self.writer.close()
+
+
+class PackedRecords:
+    """The gather path's records: packed compactly per launch and kept on this
+    GPU until the gather.  The compact-form check is collected on the device
+    and read once after the last launch (`check`; a per-launch read would stall
+    the launching thread until that launch finished)."""
+
+    def __init__(self, engine, modes: int, device):
+        self.engine, self.modes, self.device = engine, modes, device
+        self.hip = hasattr(engine, "pack_records")  # the HIP engine packs in one kernel
+        self.bad = torch.zeros((), dtype=torch.int32 if self.hip else torch.bool, device=device)
+        self.parts = []
+
+    def add(self, outs) -> None:
+        if self.hip:
+            self.parts.append(self.engine.pack_records(outs, self.modes, None, self.bad))
+        else:
+            self.parts.append(shard.pack(outs, None, self.device, modes=self.modes, validate=self.bad))
+
+    def check(self) -> None:
+        if self.parts:
+            shard.check_flag(self.bad)
+
+    def slab(self, words: int) -> torch.Tensor:
+        mine = torch.cat(self.parts) if self.parts else torch.empty(0, dtype=torch.int32, device=self.device)
+        return torch.cat([mine, mine.new_zeros(words - mine.numel())])
+
+
+def _launch_all(a, engine, batches, uploader: Uploader, sink: LogSink, packed: PackedRecords,
+                streams: _Streams) -> list:
+    """The hot path: this block's launches.  Returns the timing event pair of
+    each (none on a CPU rank); stops early once the writer thread has failed."""
     spans = []
     for b, batch in enumerate(batches):
-        up_ready[b].wait()
-        if up_err:
-            up_stop.set()
-            raise up_err[0]
-        jobs = []
-        for poc, refs in batch:
-            rl = ref_list(poc)
-            jobs.append((d_orig[poc], [d_recon[rl[r]] for r in refs], lambda_for_poc(a.qp, poc),
-                         engine.alloc_poc(len(refs), modes)))
-        if cuda:
-            compute.wait_event(up_ev[b])
+        up_event = uploader.wait(b)
+        jobs = [(*uploader.frames(poc, refs), lambda_for_poc(a.qp, poc),
+                 engine.alloc_poc(len(refs), a.mode_mask)) for poc, refs in batch]
+        if streams.cuda:
+            streams.compute.wait_event(up_event)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        engine.affine_me_batch(jobs, modes, a.extra)
-        if cuda:
+        engine.affine_me_batch(jobs, a.mode_mask, a.extra)
+        if streams.cuda:
             e1.record()
             spans.append((e0, e1))
-        if writes_own:
-            slot = slots.free.get()
-            if slot < 0:
+        outs = [j[3] for j in jobs]
+        if sink.role.download:
+            if not sink.download(batch, outs):
                 break
-            host = []
-            if cuda:
-                dnstream.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(dnstream) if cuda else contextlib.nullcontext():
-                for i, job in enumerate(jobs):
-                    h = {}
-                    for key, (c, p) in job[3].items():
-                        hc = slots.host_like(slot, (i, key, 0), c)
-                        hp = slots.host_like(slot, (i, key, 1), p)
-                        hc.copy_(c, non_blocking=cuda)
-                        hp.copy_(p, non_blocking=cuda)
-                        if cuda:  # the launch's buffers stay allocated until the copy ran
-                            c.record_stream(dnstream)
-                            p.record_stream(dnstream)
-                        h[key] = (hc, hp)
-                    host.append(h)
-                ev = None
-                if cuda:
-                    ev = torch.cuda.Event()
-                    ev.record(dnstream)
-            work.put((ev, slot, batch, host))
-        elif a.log:  # gather path: compact records stay on this GPU until the gather
-            if hip_pack:
-                slab_parts.append(engine.pack_records([j[3] for j in jobs], modes, None, pack_bad))
-            else:
-                slab_parts.append(shard.pack([j[3] for j in jobs], None, device, modes=modes,
-                                             validate=pack_bad))
-    work.put(None)
-    th.join()
-    up_stop.set()
-    up_th.join()
-    if err:
-        raise err[0]
-    if overlap:  # parsed in the uploader thread, beside the launches
-        T["read_csv_s"] += parse_s[0]
+        elif sink.role.pack:
+            packed.add(outs)
+    return spans
+
+
+def exchange_sizes(dist, world: int, rank: int, mine: list[int]) -> list[int]:
+    """The byte counts per file of every rank's block, shared by one
+    all_reduce; returns this rank's offsets: the sizes of the ranks before it."""
+    sizes = torch.zeros((world, len(mine)), dtype=torch.int64)
+    sizes[rank] = torch.tensor(mine, dtype=torch.int64)
+    _all_reduce_cpu(dist, sizes)
+    return sizes[:rank].sum(0).tolist()
+
+
+def gather_records(a, world: int, n_cus, packed: PackedRecords, sink: LogSink, dist) -> float:
+    """--gather-records: one gather of equal-size slabs brings every rank's
+    packed records to rank 0, which formats and writes them POC by POC.
+    Returns the time the gather took."""
+    t = time.perf_counter()
+    modes = a.mode_mask
+    shards = [shard.pair_shard(a.frames, world, r) for r in range(world)]
+    slab = packed.slab(max(shard.slab_words(shard.block_layout(s, modes, n_cus)) for s in shards))
+    if dist.get_backend() == "gloo":
+        slab = slab.cpu()
+    slabs = shard.gather_to_root(slab, world, 0)
+    sink.streams.synchronize()
+    gather_s = time.perf_counter() - t
+    if slabs is not None:  # rank 0
+        t0 = time.perf_counter()
+        for r in range(0 if sink.role.unpack_own else 1, world):
+            o = 0
+            for poc, refs in shards[r]:
+                w = shard.poc_words(len(refs), modes, n_cus)
+                sink.write(poc, refs, shard.unpack(slabs[r][o:o + w], [(len(refs), modes, n_cus)])[0])
+                o += w
+        sink.log_write_s += time.perf_counter() - t0
+    return gather_s
+
+
+def place_block(a, world: int, rank: int, sink: LogSink, dist) -> None:
+    """The default path's end: every rank's block into the final files at its
+    byte offsets (the sizes of the ranks before it), all ranks in parallel.
+    Rank 0 has appended its block already and only reports its sizes; without
+    the exchange (--rank-only K) the block goes into its part files alone."""
+    role = sink.role
+    mine = (sink.writer.held_sizes() if role.place else
+            [os.path.getsize(n) if os.path.exists(n) else 0 for n in logs.log_names(a.log)])
+    offsets = exchange_sizes(dist, world, rank, mine) if role.exchange else [0] * len(mine)
+    if role.place:
+        sink.writer.flush_at(offsets)
+        sink.close()
+
+
+def merge(a, world: int) -> float:
+    """--merge-parts: rank 0 appends the part files; returns the time it took."""
+    t = time.perf_counter()
+    logs.merge_parts(a.log, world, pred_mask(a.mode_mask))
+    return time.perf_counter() - t
+
+
+def _end_phase(a, world: int, rank: int, n_cus, packed: PackedRecords, sink: LogSink, dist) -> dict:
+    """What is left after the last launch, by the rank's role; the collectives
+    in the same order on every rank (gather, or the size exchange; barrier)."""
+    role, T = sink.role, {"gather_s": 0.0, "merge_s": 0.0}
+    if role.gather:
+        T["gather_s"] = gather_records(a, world, n_cus, packed, sink, dist)
+    if not role.place:
+        sink.close()  # rank 0's final files, or this rank's part files, are complete
+    if role.place or role.exchange:
+        t = time.perf_counter()
+        place_block(a, world, rank, sink, dist)
+        if role.place:
+            T["merge_s"] = time.perf_counter() - t
+    if role.barrier:
+        dist.barrier()  # every block is in place (or in its part files)
+    if role.merge:
+        T["merge_s"] = merge(a, world)
+    return T
+
+
+def _timings(rank: int, blocks, ingest: Ingest, uploader: Uploader, sink: LogSink, spans, ends: dict,
+             t_start: float) -> dict:
+    """The rank's timing record, from what each step measured (all threads
+    joined, the device idle)."""
+    T = {"rank": rank, "pairs": sum(len(r) for _, r in blocks), "pocs": len(blocks),
+         "read_csv_s": 0.0, "kernel_s": 0.0, "log_write_s": sink.log_write_s, "log_bytes": sink.log_bytes,
+         **ends, **ingest.T}
+    if uploader.first_frames_s is not None:
+        T["first_frames_s"] = uploader.first_frames_s
+    if ingest.overlap:  # parsed in the uploader thread, beside the launches
+        T["read_csv_s"] += ingest.parse_s
         T["read_csv_overlapped"] = True
-    if slab_parts:
-        shard.check_flag(pack_bad)
-    if cuda:
-        torch.cuda.synchronize()
+    if spans:
         T["kernel_s"] = sum(x.elapsed_time(y) for x, y in spans) * 1e-3
-        if spans:  # GPU idle between this rank's launches
-            T["gpu_gaps_s"] = spans[0][0].elapsed_time(spans[-1][1]) * 1e-3 - T["kernel_s"]
-
-    # ---- the decision-log gather into rank 0 (default path)
-    if gather_path and (world > 1 or self_gather):
-        t = time.perf_counter()
-        words = max(shard.slab_words(shard.block_layout(shard.pair_shard(a.frames, world, r), modes, n_cus))
-                    for r in range(world))
-        mine = torch.cat(slab_parts) if slab_parts else torch.empty(0, dtype=torch.int32, device=device)
-        slab = torch.cat([mine, mine.new_zeros(words - mine.numel())])
-        if dist.get_backend() == "gloo":
-            slab = slab.cpu()
-        slabs = shard.gather_to_root(slab, world, 0)
-        if cuda:
-            torch.cuda.synchronize()
-        T["gather_s"] = time.perf_counter() - t
-        if rank == 0:
-            t0 = time.perf_counter()
-            for r in range(0 if self_gather else 1, world):
-                o = 0
-                for poc, refs in shard.pair_shard(a.frames, world, r):
-                    w = shard.poc_words(len(refs), modes, n_cus)
-                    res = shard.unpack(slabs[r][o:o + w], [(len(refs), modes, n_cus)])[0]
-                    o += w
-                    results = {(refs[j], name): (c.cpu().numpy(), p.cpu().numpy())
-                               for (j, name), (c, p) in res.items()}
-                    T["log_bytes"] += logs.write_poc(prefix, W, H, poc, results, writer=writer)
-            T["log_write_s"] += time.perf_counter() - t0
-        del slabs
-    if writer is not None and rank == 0:
-        writer.close()
-
-    # ---- the default path: every rank's block into the final files at its
-    # byte offsets (the sizes of the ranks before it), all ranks in parallel
-    if writer is not None and rank > 0 and path == "parts":
-        writer.close()  # its part files are complete
-    elif writer is not None and rank > 0:
-        t = time.perf_counter()
-        held = writer.held_sizes()
-        if dist is None:  # --rank-only K: its block alone, into its part files
-            offsets = [0] * len(held)
-        else:
-            names = writer.files()
-            sizes = torch.zeros((world, len(names)), dtype=torch.int64)
-            sizes[rank] = torch.tensor(held, dtype=torch.int64)
-            _all_reduce_cpu(dist, sizes)
-            offsets = sizes[:rank].sum(0).tolist()
-        writer.flush_at(offsets)
-        writer.close()
-        T["merge_s"] = time.perf_counter() - t
-    elif world > 1 and a.log and path == "place" and dist is not None and rank == 0:
-        names = logs.log_names(a.log)
-        sizes = torch.zeros((world, len(names)), dtype=torch.int64)
-        sizes[0] = torch.tensor([os.path.getsize(n) if os.path.exists(n) else 0 for n in names])
-        _all_reduce_cpu(dist, sizes)
-    if world > 1 and a.log and path != "gather" and dist is not None:
-        barrier()  # every block is in place (or in its part files)
-    if path == "parts" and a.merge_parts and rank == 0 and world > 1 and a.log:
-        t = time.perf_counter()
-        logs.merge_parts(a.log, world, pred_mask(modes))
-        T["merge_s"] = time.perf_counter() - t
+        # GPU idle between this rank's launches
+        T["gpu_gaps_s"] = spans[0][0].elapsed_time(spans[-1][1]) * 1e-3 - T["kernel_s"]
     T["overall_s"] = time.perf_counter() - t_start
     return T
+
+
+def run_rank(a, world: int, rank: int, engine, device, dist=None) -> dict:
+    """One rank's whole run; returns its timings.  `engine` needs n_cus,
+    alloc_poc and affine_me_batch (vame.engine.Engine on the GPU; the tests
+    pass an oracle-backed stand-in on CPU ranks).  Whatever way it ends, the
+    uploader is stopped and joined, the writer thread ended and joined, the
+    device drained and the LogWriter closed, in that order, and the first
+    error is the one raised."""
+    t_start = time.perf_counter()
+    n_cus = (engine.n_cus(0), engine.n_cus(1))
+    role = logs.log_role(a.log, a.log_path, world, rank, dist is not None, a.merge_parts)
+    blocks = shard.pair_shard(a.frames, world, rank)
+    ingest = Ingest(a, world, rank, dist, blocks)
+    batches = launch_batches(blocks, int(os.environ.get("VAME_FIRST_LAUNCH_PAIRS", "8")) if ingest.overlap
+                             else MAX_PAIRS)
+    streams = _Streams(device)
+    uploader = Uploader(ingest, batches, streams, t_start)
+    sink = LogSink(role, a.W, a.H, streams)
+    with _owned(uploader.stop_and_join, sink.end_and_join, streams.synchronize, sink.close):
+        uploader.start()
+        sink.open()
+        packed = PackedRecords(engine, a.mode_mask, device)
+        spans = _launch_all(a, engine, batches, uploader, sink, packed, streams)
+        uploader.stop_and_join()
+        sink.end_and_join()
+        packed.check()
+        streams.synchronize()
+        ends = _end_phase(a, world, rank, n_cus, packed, sink, dist)
+    return _timings(rank, blocks, ingest, uploader, sink, spans, ends, t_start)
 
 
 def line_index(path: str, world: int, rank: int, dist, T: dict):

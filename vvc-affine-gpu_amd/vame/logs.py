@@ -5,6 +5,7 @@ frame ingest (main.cpp:293-330) and the per-CU decision log
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -89,6 +90,53 @@ def log_names(prefix: str, pred_mask: int = 15) -> list[str]:
 def part_prefix(prefix: str, rank: int) -> str:
     """The prefix of rank `rank`'s part files (vame.distrun --shard-logs)."""
     return f"{prefix}.part{rank}"
+
+
+@dataclasses.dataclass(frozen=True)
+class LogRole:
+    """What one rank of a frame-sharded run does for the decision logs
+    (`log_role`; the three paths are described in vame/distrun.py)."""
+    prefix: str = ""           # of the files this rank writes: the final ones or its part files
+    remove_old: bool = False   # removeOldTraces (main.cpp:469) on that prefix first
+    writer: str = "none"       # its LogWriter: "none", "append" (as it goes) or "deferred" (rows held)
+    download: bool = False     # each launch's records come to the host and are formatted here ...
+    pack: bool = False         # ... or are packed on the device and kept there for the gather
+    gather: bool = False       # takes part in the records gather into rank 0
+    unpack_own: bool = False   # rank 0 writes its own slab too (a one-rank group)
+    exchange: bool = False     # takes part in the byte-count all_reduce
+    place: bool = False        # writes its held rows at its offsets (0 without the exchange)
+    barrier: bool = False      # waits for every rank's files before the run ends
+    merge: bool = False        # appends the part files to the final ones after the barrier
+
+
+def log_role(log: str, log_path: str, world: int, rank: int, grouped: bool,
+             merge: bool = False) -> LogRole:
+    """The one decision of who writes what: `log` the -l prefix ("" for no
+    logs), `log_path` "place" / "parts" / "gather", `grouped` whether the ranks
+    share a process group (not under --rank-only), `merge` --merge-parts.
+    Rank 0 appends to the final files as it goes.  Every other rank: "place"
+    holds its rows (a deferred writer) and writes them into the final files at
+    the offsets the exchange gives -- without a group into its part files at
+    offset 0, which is why those are removed first: nothing truncates them;
+    "parts" appends to its part files; "gather" packs its records for rank 0.
+    In a one-rank group rank 0's own records take the gather path too, so the
+    collective and the writing from gathered slabs run on one GPU.  Every field
+    that names a collective depends on (log, log_path, world, grouped) only, so
+    the ranks of a run agree on it."""
+    if not log:
+        return LogRole()
+    gather = log_path == "gather" and grouped
+    own_slab = gather and world == 1
+    download = (rank == 0 or log_path != "gather") and not own_slab
+    final = rank == 0 or (grouped and log_path != "parts")
+    place = rank > 0 and log_path == "place"
+    return LogRole(prefix=log if final else part_prefix(log, rank),
+                   remove_old=rank == 0 or not grouped or log_path == "parts",
+                   writer="deferred" if place else "append" if download or own_slab else "none",
+                   download=download, pack=not download, gather=gather, unpack_own=own_slab,
+                   exchange=log_path == "place" and grouped and world > 1, place=place,
+                   barrier=log_path != "gather" and grouped and world > 1,
+                   merge=log_path == "parts" and merge and rank == 0 and world > 1)
 
 
 def merge_parts(prefix: str, n_parts: int, pred_mask: int = 15) -> int:
